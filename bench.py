@@ -1,23 +1,34 @@
 #!/usr/bin/env python3
 """bench.py -- forward+adjoint timesteps/s of the Hermite stepper on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one complete gradient evaluation of the workload
 (discrete_adjoint!(..., history_precomputed=false): control tables, step propagators,
 forward sweep, guard forcing, terminal condition, adjoint sweep, gradient), host to host
-(pcof in, gradient out), through the C ABI.  value = nsteps * K / elapsed.
+(pcof in, gradient out), through the C ABI.  value = nsteps * K / elapsed;
+ms_per_step = elapsed / K.
 
 Workload (BASELINE.json configs[2]): 3-qubit dispersive CNOT,
 subsystems (4,4,4), N=64, 8 initial-condition columns, 3 control operators, Hermite order 8,
 tf=550, dt=1 (nsteps=550), fp64; 180 B-spline-with-carrier coefficients, seed 0.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--dump-outputs DIR writes what the last timed step returned to its caller, float64:
+  DIR/grad.npy  the gradient [180];
+  DIR/out3.npy  the scalars { <w_N,R>, <w_N,T>, guard penalty } (include/qgd.h).
+
+--full adds everything else the line has carried, measured after the timed steps except
+for the roofline's live sample:
   roofline      the dominant kernel (largest share of device time): algorithmic flops or
                 bytes per launch / its mean duration measured with HIP events on the
-                library's stream, against the gfx950 peak;
+                library's stream (one sampled step in 16 of the timed steps), against the
+                gfx950 peak; per-phase breakdown;
+  settled, forward-only, with_history, collectives, the other split, weak scaling,
+  cnot2 (C2) and large_n (C5) on the GPU;
   cpu_baseline  the oracle (CPU restatement of the reference algorithm) timed on this
                 host on a bounded sample of the same workload.
+The --no-* switches leave out single parts of --full.
 """
 import argparse
 import gc
@@ -434,6 +445,11 @@ def main():
                     help="extra untimed evaluations after the W warm-up steps (the card's clocks settle after ~20 ms of work, "
                          "scripts/clock_profile.py); 0 = the contract's plain 'W warm-up, K timed'; recorded as run_in_steps")
     ap.add_argument("--nsteps", type=int, default=550, help="timesteps of the workload (tf = nsteps, dt = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the gradient and scalars of the last timed step as DIR/grad.npy and DIR/out3.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline sample and per-phase breakdown, settled clocks, "
+                         "forward-only, with_history, the other split, weak scaling, collectives, cnot2, large_n, cpu_baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-large-n", action="store_true", help="skip the secondary C5 (N=256) measurement")
     ap.add_argument("--no-cnot2", action="store_true", help="skip the secondary C2 (cnot2) measurement")
@@ -452,6 +468,8 @@ def main():
     ap.add_argument("--no-other-split", action="store_true", help="N > 1: do not time the other split (columns beside time windows) in the same line")
     ap.add_argument("--oversubscribe", action="store_true", help="let several ranks share a GPU (test boxes with one GPU; with --comm torch --backend gloo)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Started bare with --gpus N: become the launcher of N ranks (one process per GPU) BEFORE anything touches the
@@ -545,18 +563,21 @@ def main():
     # code objects (0.4 ms) -- else the largest; the choice is checked against the per-phase breakdown taken AFTER the timed
     # region (`phases_ms_all_events`: all 13 phases bracketed, ~0.17 ms of event records per evaluation; round 3 took it from
     # the warm-up steps, which made them 1.5x as long as a timed step and mostly idle) and the line says so
-    # (`roofline.dominant_confirmed`).
+    # (`roofline.dominant_confirmed`).  All of this is --full only: a plain run's warm-up steps are plain evaluations.
     merge = (("sweep_forward2", "sweep_forward"), ("sweep_adjoint2", "sweep_adjoint"))
-    dp.set_timing(1)
-    dp.discrete_adjoint(pcof)
-    first = dp.timings()
-    nbr = 1
+    nbr = 0
+    if args.full:
+        dp.set_timing(1)
+        dp.discrete_adjoint(pcof)
+        first = dp.timings()
+        nbr = 1
     dp.set_timing(0)
     inner = getattr(dp, "dp", dp)
     path = inner.operator_path() if hasattr(inner, "operator_path") else ("sparse", 0, 0)
-    model = phase_model(prob.N_tot_levels, prob.N_initial_conditions, order // 2, prob.N_operators, args.nsteps + 1,
-                        sparse_ops=(path[0] == "sparse"), fused_propagator=("propagator" not in first))
-    dom_raw = next((k for k in ("front", "inverse") if k in first and k in model), None) or max((k for k in first if k in model), key=first.get)
+    if args.full:
+        model = phase_model(prob.N_tot_levels, prob.N_initial_conditions, order // 2, prob.N_operators, args.nsteps + 1,
+                            sparse_ops=(path[0] == "sparse"), fused_propagator=("propagator" not in first))
+        dom_raw = next((k for k in ("front", "inverse") if k in first and k in model), None) or max((k for k in first if k in model), key=first.get)
     for _ in range(max(args.warmup, 1) - nbr + args.run_in):
         dp.discrete_adjoint(pcof)
     phase_ms = {}
@@ -570,7 +591,7 @@ def main():
     # between kernels) and +30 us for reading the pair back (stream synchronisation + elapsed-time query).  Round 3
     # bracketed every 8th step and read inside the loop: 9 us per step on average over 20 steps.  Now: one bracketed step
     # per 16 (the middle one of a 20-step region), read back only when the next bracketed step is about to overwrite the
-    # pair -- the last one after the timed region.
+    # pair -- the last one after the timed region.  A plain run (no --full) samples nothing.
     pending = False
 
     def read_sample():
@@ -578,10 +599,10 @@ def main():
             phase_ms[k] = phase_ms.get(k, 0.0) + v
 
     for i in range(args.steps):
-        sample = (i % 16 == min(10, args.steps // 2))
+        sample = args.full and (i % 16 == min(10, args.steps // 2))
         if sample and pending:
             read_sample(); pending = False
-        if sample or (i > 0 and (i - 1) % 16 == min(10, args.steps // 2)):
+        if args.full and (sample or (i > 0 and (i - 1) % 16 == min(10, args.steps // 2))):
             dp.set_timing(2 if sample else 0, dom_raw)
         grad, out3 = dp.discrete_adjoint(pcof)
         if step_times is not None:
@@ -593,20 +614,26 @@ def main():
     elapsed = max_over_ranks(time.perf_counter() - t0)
     if pending:
         read_sample(); pending = False
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received from its last step (every rank holds the same reduced result)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "grad.npy"), np.asarray(grad, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "out3.npy"), np.asarray(out3, dtype=np.float64))
     # per-phase breakdown: three evaluations with every phase bracketed (untimed, after the timed region)
     breakdown = {}
-    dp.set_timing(1)
-    for _ in range(3):
-        dp.discrete_adjoint(pcof)
-        for k, v in dp.timings().items():
-            breakdown[k] = breakdown.get(k, 0.0) + v / 3
-    dp.set_timing(0)
+    if args.full:
+        dp.set_timing(1)
+        for _ in range(3):
+            dp.discrete_adjoint(pcof)
+            for k, v in dp.timings().items():
+                breakdown[k] = breakdown.get(k, 0.0) + v / 3
+        dp.set_timing(0)
     if step_times:
         print("[bench] us per timed step:", " ".join(f"{(b - a) * 1e6:.0f}" for a, b in zip([t0] + step_times[:-1], step_times)), file=sys.stderr)
     part_info = getattr(inner, "partition", None)
     # the collectives of one evaluation, timed by HIP events on the library's stream (--comm lib)
     comm_ms = None
-    if use_dist and args.comm == "lib":
+    if args.full and use_dist and args.comm == "lib":
         dp.set_timing(1)
         acc = {}
         for _ in range(5):
@@ -620,7 +647,7 @@ def main():
     # (nsteps = 550 per GPU, dt unchanged), i.e. per-GPU work fixed -- where a 0.44 ms evaluation has no more
     # per-rank latency to give, this is what the time-window partition is for.  Reported as `weak_in_time`.
     weak = None
-    if use_dist and args.shard == "time" and (world > 1 or os.environ.get("QGD_BENCH_WEAK")):
+    if args.full and use_dist and args.shard == "time" and (world > 1 or os.environ.get("QGD_BENCH_WEAK")):
         try:
             dp.close()
             nsteps_w = args.nsteps * world
@@ -646,7 +673,7 @@ def main():
     # its clock ramp (scripts/clock_profile.py: 345 us per evaluation in the first 7 ms of work, 328-335 afterwards); an
     # optimisation runs thousands of evaluations back to back.  Reported as `settled`, never as `value`.
     settled = None
-    if not use_dist:
+    if args.full and not use_dist:
         try:
             dp.set_timing(0)
             for _ in range(40):
@@ -665,7 +692,7 @@ def main():
             settled = {"error": repr(exc)}
     # forward-only (eval_forward: tables .. history, guard, overlaps), reported beside the metric
     fwd_elapsed = None
-    if not use_dist:
+    if args.full and not use_dist:
         dp.set_timing(0)
         dp.eval_forward(pcof)
         settle()
@@ -681,7 +708,7 @@ def main():
     # the three arrays downloaded in the reference layout (31.6 MB), registered (pinned) once as INTEGRATION.md's shim
     # does, and unregistered (pageable).  Reported beside `value`, never as `value`.
     with_hist = None
-    if not use_dist and not args.no_with_history:
+    if args.full and not use_dist and not args.no_with_history:
         try:
             n2, m1, ntp, cc = prob.real_system_size, 1 + order // 2, 1 + prob.nsteps, prob.N_initial_conditions
             with_hist = {"bytes_per_evaluation": 8 * (n2 * m1 * ntp * cc + 2 * n2 * ntp * cc)}
@@ -712,7 +739,7 @@ def main():
     # timed the same way (W warm-up, K timed steps, barrier + max over ranks, its own communicator) and reported as
     # `north_star_split` (or `time_window_split` when --shard columns made the columns the headline).
     other_split = None
-    if use_dist and (world > 1 or args.force_dist) and not args.no_other_split:
+    if args.full and use_dist and (world > 1 or args.force_dist) and not args.no_other_split:
         other = "columns" if args.shard == "time" else "time"
         try:
             if other == "columns" and world > prob.N_initial_conditions:
@@ -758,43 +785,16 @@ def main():
 
     # N > 1: C5 under the same partition (every rank takes part; secondary number, must never cost the headline one)
     large_dist = None
-    if use_dist and world > 1 and not args.no_large_n:
+    if args.full and use_dist and world > 1 and not args.no_large_n:
         try:
             large_dist = large_n_partitioned(qgd, np, args, rank, world, local_rank, uid)
         except Exception as exc:
             large_dist = {"error": repr(exc)}
 
     if rank == 0:
-        for k in phase_ms:
-            phase_ms[k] /= nsamp
-        # the dominant kernel among the single-launch phases, timed live in the timed region
-        dom = dom_raw
-        timed = {dom: phase_ms[dom_raw]}
-        bound, work = model[dom]
-        for extra, base in merge:
-            if extra in breakdown:
-                breakdown[base] = breakdown.get(base, 0.0) + breakdown.pop(extra)
-        if bound == "mfma":
-            achieved = work / (timed[dom] * 1e-3) / 1e12
-            peak, unit = PEAK_FP64_MATRIX_TFLOPS, "TFLOP/s"
-        else:
-            achieved = work / (timed[dom] * 1e-3) / 1e9
-            peak, unit = PEAK_HBM_GBS, "GB/s"
         # N > 1: ONE evaluation is spread over the ranks (strong scaling)
         total_timesteps = args.nsteps * args.steps
         sec_eval = elapsed / args.steps
-        # what the committed profiles say about the dominant kernel belongs to the profiled workload only (550 steps on one GPU)
-        profiled = (args.nsteps == 550 and not use_dist)
-        traffic, traffic_source = measured_traffic(dom) if profiled else (None, None)
-        prof_ms, prof_src = profiled_launch_ms(dom) if profiled else (None, None)
-        N_, c_, m_ = prob.N_tot_levels, prob.N_initial_conditions, order // 2
-        # the only HBM-proportional term of the ALGORITHM is the history stream, written once and read
-        # once: B_step = 2*16*N*(1+m)*c + 2*16*N*c bytes per timestep
-        b_step = 2 * 16 * N_ * (1 + m_) * c_ + 2 * 16 * N_ * c_
-        hs = b_step * args.nsteps / sec_eval / 1e9
-        blocks = part_info["blocks"] if part_info else min(64, int(round(args.nsteps ** (2.0 / 3.0))))
-        blen = part_info["block_len"] if part_info else -(-args.nsteps // max(blocks, 1))
-        gflop = executed_gflop(N_, c_, m_, prob.N_operators, args.nsteps, -(-args.nsteps // blen), blen, path[0] == "sparse", front=("front" in first))
         if args.comm == "lib":
             how = "RCCL collectives issued inside libqgd_hip.so (qgd_comm_init_rccl)"
         else:
@@ -805,60 +805,90 @@ def main():
             "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "run_in_steps": args.run_in,
             "ms_per_step": sec_eval * 1e3,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
+            "dtype": "f64", "data": "synthetic", "full": args.full,
             "python_gc": "collected between the timed regions, disabled inside them (as timeit does): one full collection is 40-75 ms",
             "config": {"workload": "cnot3 dispersive CNOT (4,4,4)/(2,2,2), N=64, 8 columns, 3 controls x 60 coeffs, "
                                    f"Hermite order 8, tf={args.nsteps}, nsteps={args.nsteps}, one full discrete_adjoint! per step",
                        "parallelism": "1 GPU" if not use_dist else
                                       ((f"time windows over {n_gpus} GPUs, 2 all-gathers + 1 all-reduce per evaluation" if args.shard == "time"
                                         else f"column blocks over {n_gpus} GPUs, 2 all-reduces per evaluation") + "; " + how)},
-            "roofline": {"kernel": KERNEL_OF_PHASE.get(dom, dom), "phase": dom, "bound": bound, "achieved": achieved, "peak": peak, "unit": unit,
-                         "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_source, "mfma_pipe_busy_pmc": measured_mfma_util(dom) if profiled else None,
-                         "launch_ms": timed[dom], "launches_timed": nsamp, "algorithmic_work_per_launch": work,
-                         "launch_ms_profile": prof_ms, "launch_ms_profile_source": prof_src,
-                         "launch_ms_note": "launch_ms: HIP event pair on the library's stream around the launch, inside the timed region -- it also covers "
-                                           "the dispatch of the grid behind the drained queue and the end-of-kernel signal (5-8 us); the rocprofv3 "
-                                           "figure is first wave to last wave.  frac uses launch_ms",
-                         # (single-launch phases only: the sweeps are several launches each)
-                         "dominant_confirmed": bool(max((k for k in breakdown if k in model and not k.startswith("sweep")), key=breakdown.get, default=dom) == dom),
-                         "history_stream": {"bound": "hbm", "bytes_per_timestep": b_step, "achieved": hs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                            "frac": hs / PEAK_HBM_GBS, "note": "SURVEY 8(d) B_step * nsteps / T_eval: the algorithm's history stream "
-                                                                               "(write once, read once) against HBM; the evaluation is latency-bound, not stream-bound"},
-                         "whole_evaluation": {"bound": "mfma", "executed_gflop": gflop, "achieved": gflop / sec_eval / 1e3, "peak": PEAK_FP64_MATRIX_TFLOPS,
-                                              "unit": "TFLOP/s", "frac": gflop / sec_eval / 1e3 / PEAK_FP64_MATRIX_TFLOPS,
-                                              "note": "flops the kernels execute (bench.py executed_gflop), all phases, / wall time of one evaluation"}},
-            "phases_ms_all_events": {k: round(v, 4) for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1])},
             "operator_path": path[0],
-            "settled": settled,
-            "collectives_ms": comm_ms,
-            ("north_star_split" if args.shard == "time" else "time_window_split"): other_split,
-            "weak_in_time": weak,
-            "with_history_ms_per_step": None if not with_hist else with_hist.get("pinned_ms_per_step"),
-            "with_history": with_hist,
-            "forward_only_timesteps_per_s": (total_timesteps / fwd_elapsed) if fwd_elapsed else None,
             "infidelity": float(1 - (out3[0] ** 2 + out3[1] ** 2) / prob.N_ess_levels ** 2),
             "grad_norm": float(np.linalg.norm(grad)),
         }
-        if not use_dist:
-            dp.close()
-            # (round 4 tried these two BEFORE the headline, to start its timed region on a card that had been working: `value`
-            #  did not move -- 0.3328 against 0.3314 ms -- and the pinned downloads of `with_history` behind a C5 evaluation in
-            #  the same process took 3.3-3.9 ms instead of 0.87; the order of round 3 stays)
-            if not args.no_cnot2:
-                try:
-                    out["cnot2"] = cnot2_case_gpu(qgd, np)
-                except Exception as exc:
-                    out["cnot2"] = {"error": repr(exc)}
-            if not args.no_large_n:
-                try:                      # a secondary measurement must never cost the headline line
-                    out["large_n"] = large_n_case(qgd, np)
-                except Exception as exc:
-                    out["large_n"] = {"error": repr(exc)}
-        if large_dist is not None:
-            out["large_n"] = large_dist
-        if not args.no_cpu_baseline:
-            orc = import_oracle()
-            out["cpu_baseline"] = cpu_baseline(qgd, orc)
+        if args.full:
+            for k in phase_ms:
+                phase_ms[k] /= nsamp
+            # the dominant kernel among the single-launch phases, timed live in the timed region
+            dom = dom_raw
+            timed = {dom: phase_ms[dom_raw]}
+            bound, work = model[dom]
+            for extra, base in merge:
+                if extra in breakdown:
+                    breakdown[base] = breakdown.get(base, 0.0) + breakdown.pop(extra)
+            if bound == "mfma":
+                achieved = work / (timed[dom] * 1e-3) / 1e12
+                peak, unit = PEAK_FP64_MATRIX_TFLOPS, "TFLOP/s"
+            else:
+                achieved = work / (timed[dom] * 1e-3) / 1e9
+                peak, unit = PEAK_HBM_GBS, "GB/s"
+            # what the committed profiles say about the dominant kernel belongs to the profiled workload only (550 steps on one GPU)
+            profiled = (args.nsteps == 550 and not use_dist)
+            traffic, traffic_source = measured_traffic(dom) if profiled else (None, None)
+            prof_ms, prof_src = profiled_launch_ms(dom) if profiled else (None, None)
+            N_, c_, m_ = prob.N_tot_levels, prob.N_initial_conditions, order // 2
+            # the only HBM-proportional term of the ALGORITHM is the history stream, written once and read
+            # once: B_step = 2*16*N*(1+m)*c + 2*16*N*c bytes per timestep
+            b_step = 2 * 16 * N_ * (1 + m_) * c_ + 2 * 16 * N_ * c_
+            hs = b_step * args.nsteps / sec_eval / 1e9
+            blocks = part_info["blocks"] if part_info else min(64, int(round(args.nsteps ** (2.0 / 3.0))))
+            blen = part_info["block_len"] if part_info else -(-args.nsteps // max(blocks, 1))
+            gflop = executed_gflop(N_, c_, m_, prob.N_operators, args.nsteps, -(-args.nsteps // blen), blen, path[0] == "sparse", front=("front" in first))
+            out.update({
+                "roofline": {"kernel": KERNEL_OF_PHASE.get(dom, dom), "phase": dom, "bound": bound, "achieved": achieved, "peak": peak, "unit": unit,
+                             "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_source, "mfma_pipe_busy_pmc": measured_mfma_util(dom) if profiled else None,
+                             "launch_ms": timed[dom], "launches_timed": nsamp, "algorithmic_work_per_launch": work,
+                             "launch_ms_profile": prof_ms, "launch_ms_profile_source": prof_src,
+                             "launch_ms_note": "launch_ms: HIP event pair on the library's stream around the launch, inside the timed region -- it also covers "
+                                               "the dispatch of the grid behind the drained queue and the end-of-kernel signal (5-8 us); the rocprofv3 "
+                                               "figure is first wave to last wave.  frac uses launch_ms",
+                             # (single-launch phases only: the sweeps are several launches each)
+                             "dominant_confirmed": bool(max((k for k in breakdown if k in model and not k.startswith("sweep")), key=breakdown.get, default=dom) == dom),
+                             "history_stream": {"bound": "hbm", "bytes_per_timestep": b_step, "achieved": hs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                                "frac": hs / PEAK_HBM_GBS, "note": "SURVEY 8(d) B_step * nsteps / T_eval: the algorithm's history stream "
+                                                                                   "(write once, read once) against HBM; the evaluation is latency-bound, not stream-bound"},
+                             "whole_evaluation": {"bound": "mfma", "executed_gflop": gflop, "achieved": gflop / sec_eval / 1e3, "peak": PEAK_FP64_MATRIX_TFLOPS,
+                                                  "unit": "TFLOP/s", "frac": gflop / sec_eval / 1e3 / PEAK_FP64_MATRIX_TFLOPS,
+                                                  "note": "flops the kernels execute (bench.py executed_gflop), all phases, / wall time of one evaluation"}},
+                "phases_ms_all_events": {k: round(v, 4) for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1])},
+                "settled": settled,
+                "collectives_ms": comm_ms,
+                ("north_star_split" if args.shard == "time" else "time_window_split"): other_split,
+                "weak_in_time": weak,
+                "with_history_ms_per_step": None if not with_hist else with_hist.get("pinned_ms_per_step"),
+                "with_history": with_hist,
+                "forward_only_timesteps_per_s": (total_timesteps / fwd_elapsed) if fwd_elapsed else None,
+            })
+            if not use_dist:
+                dp.close()
+                # (round 4 tried these two BEFORE the headline, to start its timed region on a card that had been working: `value`
+                #  did not move -- 0.3328 against 0.3314 ms -- and the pinned downloads of `with_history` behind a C5 evaluation in
+                #  the same process took 3.3-3.9 ms instead of 0.87; the order of round 3 stays)
+                if not args.no_cnot2:
+                    try:
+                        out["cnot2"] = cnot2_case_gpu(qgd, np)
+                    except Exception as exc:
+                        out["cnot2"] = {"error": repr(exc)}
+                if not args.no_large_n:
+                    try:                      # a secondary measurement must never cost the headline line
+                        out["large_n"] = large_n_case(qgd, np)
+                    except Exception as exc:
+                        out["large_n"] = {"error": repr(exc)}
+            if large_dist is not None:
+                out["large_n"] = large_dist
+            if not args.no_cpu_baseline:
+                orc = import_oracle()
+                out["cpu_baseline"] = cpu_baseline(qgd, orc)
         print(json.dumps(out))
     try:
         dp.close()

@@ -10,8 +10,8 @@ REPO=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $REPO/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-large-n --no-with-history --no-cnot2"
-BENCH_S="python3 $REPO/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-large-n --no-with-history --no-cnot2"
+BENCH="python3 $REPO/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-large-n --no-with-history --no-cnot2"
+BENCH_S="python3 $REPO/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-large-n --no-with-history --no-cnot2"
 C5="python3 $REPO/scripts/c5_synthetic.py"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_cnot3 -- $BENCH > $OUT/bench_under_rocprof.json 2> $OUT/stats_cnot3.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c5 -- $C5 > $OUT/c5_under_rocprof.txt 2> $OUT/stats_c5.err
@@ -30,5 +30,5 @@ for W in cnot3 c5; do rm -rf $OUT/stats_$W $OUT/pmc_fetch_$W $OUT/pmc_write_$W $
 ls -la $OUT
 
 
-cd $REPO && python3 bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+cd $REPO && python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 tail -c 400 $OUT/bench.json

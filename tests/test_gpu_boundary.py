@@ -201,7 +201,7 @@ def test_bench_two_processes_share_the_gpu(shard):
     path.  The partitioned gradient must equal the single-process one, for cnot3 and for C5."""
     import json
     bench = os.path.join(ROOT, "bench.py")
-    common = ["--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--nsteps", "120"]
+    common = ["--full", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--nsteps", "120"]
     env = dict(os.environ, MASTER_PORT="29631", QGD_TINY="1")
     one = subprocess.run([sys.executable, bench, "--gpus", "1", "--no-large-n"] + common, capture_output=True, text=True, timeout=600, env=env)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -243,7 +243,7 @@ def test_bench_in_library_rccl_one_rank(shard):
     line carries the event-timed collectives."""
     import json
     bench = os.path.join(ROOT, "bench.py")
-    common = ["--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-large-n", "--no-cnot2", "--no-with-history", "--nsteps", "120"]
+    common = ["--full", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-large-n", "--no-cnot2", "--no-with-history", "--nsteps", "120"]
     env = dict(os.environ, MASTER_PORT="29633")
     one = subprocess.run([sys.executable, bench] + common, capture_output=True, text=True, timeout=600, env=env)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -258,6 +258,33 @@ def test_bench_in_library_rccl_one_rank(shard):
     other = j2["north_star_split" if shard == "time" else "time_window_split"]
     assert other and "error" not in other, other
     assert other["grad_rel_diff_vs_headline_split"] <= 1e-10 and other["collectives_ms"], other
+
+
+def test_bench_plain_run_and_dumped_outputs(qgd, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps evaluations and carries the headline only; --dump-outputs
+    writes what the last timed step returned to its caller (gradient and scalars, float64): the workload's own evaluation."""
+    import json
+    import bench
+    out_dir = tmp_path / "out"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--nsteps", "120",
+                          "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    j = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 4 and j["full"] is False and j["higher_is_better"] is True and j["dtype"] == "f64"
+    assert abs(j["value"] * j["ms_per_step"] * 1e-3 - 120) <= 1e-9 * 120
+    assert not {"roofline", "settled", "cpu_baseline", "cnot2", "large_n", "with_history"} & set(j), sorted(j)
+    grad, out3 = np.load(out_dir / "grad.npy"), np.load(out_dir / "out3.npy")
+    assert grad.dtype == np.float64 and out3.dtype == np.float64 and out3.shape == (3,)
+    assert abs(np.linalg.norm(grad) - j["grad_norm"]) <= 1e-14 * j["grad_norm"]
+    prob, ctrl, pcof, target = bench.workload(qgd, 120, 120.0)
+    dp = qgd.DeviceProblem(prob, 8, device=0)
+    try:
+        dp.set_controls(ctrl); dp.set_target(target)
+        g, o = dp.discrete_adjoint(pcof)
+    finally:
+        dp.close()
+    assert grad.shape == g.shape and np.abs(grad - g).max() <= 1e-12 * np.abs(g).max()
+    assert np.abs(out3 - o).max() <= 1e-12 * max(1.0, np.abs(o).max())
 
 
 @pytest.mark.parametrize("which,order,world", [("cnot2", 4, 2), ("cnot2", 8, 4), ("guarded", 6, 2), ("cnot3", 8, 2), ("cnot3", 8, 8),

@@ -261,7 +261,7 @@ def test_bench_default_multi_gpu_flow_between_processes(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lib = _fake_transport(tmp_path)
     env = dict(os.environ, QGD_RCCL_LIB=lib, MASTER_PORT="29657", QGD_TINY="1")
-    common = ["--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--nsteps", "120"]
+    common = ["--full", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--nsteps", "120"]
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--no-large-n"] + common,
                          capture_output=True, text=True, timeout=600, env=env)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -289,7 +289,7 @@ def test_bench_multi_gpu_flow_with_four_ranks(tmp_path):
     lib = _fake_transport(tmp_path)
     env = dict(os.environ, QGD_RCCL_LIB=lib, MASTER_PORT="29671", QGD_TINY="1")
     t0 = time.time()
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--oversubscribe", "--steps", "3", "--warmup", "2",
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--oversubscribe", "--full", "--steps", "3", "--warmup", "2",
                           "--no-cpu-baseline", "--no-large-n"], capture_output=True, text=True, timeout=600, env=env)
     assert run.returncode == 0, run.stderr[-3000:]
     assert time.time() - t0 < 400

@@ -39,24 +39,34 @@ def test_bspline_host_vs_reference_fortran_golden(qgd):
         assert not mask.any() or np.abs(B[:, mask]).max() == 0.0
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "bspline_lib.so")),
-                    reason="oracle/_ref not built (reference checkout absent)")
 def test_bspline_oracle_vs_live_reference_fortran(orc):
-    """Same check against the live compiled reference routine at fresh random points."""
-    lib = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "bspline_lib.so"))
+    """Same check against the compiled reference routine at further random points (seed 9, all k derivatives).  Where
+    oracle/_ref is built the routine is called live, and must also reproduce the stored fixture
+    tests/golden/bspline_bsplvd_live.npz (made by tests/golden/make_bspline_golden.py); elsewhere the fixture stands in."""
+    so = os.path.join(ROOT, "oracle", "_ref", "bspline_lib.so")
+    lib = C.CDLL(so) if os.path.exists(so) else None
+    live = np.load(os.path.join(ROOT, "tests", "golden", "bspline_bsplvd_live.npz"))
     rng = np.random.default_rng(9)
+    i = 0
     for deg, nb in [(2, 10), (4, 9), (16, 20)]:
         k = deg + 1; nk = nb + k; nd = nk - 2 * (k - 1)
         knots = np.concatenate([np.zeros(k - 1), np.linspace(0, 1, nd), np.ones(k - 1)])
         for x in rng.random(20):
             left = min(int(np.floor(x * (nd - 1) + k)), nk - k)
-            a = np.zeros((k, k), order="F"); out = np.zeros((k, k), order="F")
-            i64 = lambda v: C.byref(C.c_int64(v))
-            lib.bsplvd_(knots.ctypes.data_as(C.c_void_p), i64(k), C.byref(C.c_double(x)), i64(left),
-                        a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), i64(k))
+            assert (live["degree"][i], live["n_basis"][i], live["x"][i], live["left"][i]) == (deg, nb, x, left), i
+            stored = live["values"][i][:k, :k]
+            i += 1
+            out = stored
+            if lib is not None:
+                a = np.zeros((k, k), order="F"); out = np.zeros((k, k), order="F")
+                i64 = lambda v: C.byref(C.c_int64(v))
+                lib.bsplvd_(knots.ctypes.data_as(C.c_void_p), i64(k), C.byref(C.c_double(x)), i64(left),
+                            a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), i64(k))
+                assert np.all(np.abs(stored - out) <= 1e-14 * np.maximum(1.0, np.abs(out).max(axis=0, keepdims=True)))
             _, got = orc.bspline_basis_derivs(deg, nb, float(x), k)
             scale = np.maximum(1.0, np.abs(out.T).max(axis=1, keepdims=True))
             assert np.all(np.abs(got - out.T) <= 1e-12 * scale)
+    assert i == len(live["x"])
 
 
 def _controls(qgd):
