@@ -37,6 +37,40 @@ struct Phase { const char *name; int slot; hipEvent_t e0, e1; bool used; };
 }  // namespace qgdh
 using qgdh::Phase;
 
+// What the per-time-point buffers hold of the last forward sweep, and what a later call may make of it:
+//   SWEEP_NONE     nothing a history_precomputed call may refer to (none yet, a sweep in progress or one that failed, a
+//                  sweep of another kind: eval_adjoint, the forced sweep, or a setter voided it)
+//   SWEEP_GENERAL  the two-point form's sweep
+//   SWEEP_FRONT    the fused front's sweep (qgd_device.h: qgdk_ctx::front): state history, lambda and forcing are the same
+//                  quantities as ever, but L / R / Linv / P are the same-point form's -- qgd_get_intermediate redoes the
+//                  forward evaluation on the general path from pcof before it returns them
+//   SWEEP_SMALL    a small-problem evaluation (qgd_k_tiny.hip), which leaves none of its intermediates behind: only its pcof
+//                  and whether it was a gradient are kept, so that a call that needs them (history_precomputed with output
+//                  arrays, qgd_get_intermediate) redoes it on the general path
+// has_pcof, pcof: the coefficients of the sweep (has_pcof false: it ran from the control tables the caller set, pcof NULL).
+//   A setter that voids the sweep keeps them, for qgd_get_intermediate's redo of a front sweep -- except qgd_set_control_basis,
+//   whose new basis they do not fit.
+// reusable: a history_precomputed call with the same pcof may skip the sweep.  A new target or cost type clears it for
+//   SWEEP_FRONT only, whose k_psi formed L_N^-H times the terminal value of the old ones (the general path re-forms the
+//   terminal condition on reuse); kind and pcof stay, so the sweep can still be redone.
+// derivs: the stage derivatives of the stored history are in place.  Every transition that replaces the history clears it.
+// front: what qgd_get_intermediate("front_path") reports -- whether the last forward evaluation took the fused front.  A setter
+//   that voids the sweep leaves it (and the same-point matrices in the buffers).
+// New control tables void the sweep on a windowed grid only: there a reused sweep re-runs its windows from the caller's tables;
+//   on a resident grid nothing is re-run, and a NULL-pcof history_precomputed call after new tables reuses the sweep -- the
+//   caller's promise that the history belongs to them, as in the reference.
+// A call that is refused before its first launch leaves the record as it was.
+enum SweepKind { SWEEP_NONE, SWEEP_GENERAL, SWEEP_FRONT, SWEEP_SMALL };
+struct StoredSweep {
+    SweepKind kind = SWEEP_NONE;
+    bool has_pcof = false;
+    std::vector<double> pcof;
+    bool gradient = false;
+    bool reusable = false;
+    bool derivs = false;
+    bool front = false;
+};
+
 struct qgd_handle_s {
     qgdk_ctx k{};
     int order = 0, nsteps = 0, device = 0;      // nsteps: GLOBAL number of timesteps
@@ -51,7 +85,8 @@ struct qgd_handle_s {
     double *fsc_forced = nullptr, *fsc_forcing = nullptr;   // HBM work-panel slabs of the forced kernels when they exceed the LDS (N > 64)
     std::vector<void *> forcing_bufs;  // eval_forward with a user forcing
     size_t forcing_key = 0;
-    bool have_basis = false, have_tables = false, forward_valid = false, derivs_valid = false;
+    bool have_basis = false, have_tables = false;
+    StoredSweep sweep;
     std::vector<int32_t> ncoef, poff;
     std::vector<int64_t> goff;
     double *pcof_dev = nullptr;
@@ -72,18 +107,10 @@ struct qgd_handle_s {
     unsigned long long mirror_seq = 0;
     bool mirror_armed = false;          // the evaluation in flight ends with a mirrored k_contract_sum
     // Small problems (N <= 4, <= 4 columns, <= 128 time points: Rabi, the two-qubit CNOT) take the four-launch path of
-    // qgd_k_tiny.hip for calls that return only [grad | scalars].  That path leaves none of the general path's intermediates
-    // behind: history_stale makes a later call that needs them (history_precomputed with output arrays, qgd_get_intermediate)
-    // redo the evaluation on the general path first.  QGD_TINY=0 / qgd_set_small_path(h, 0): off.
+    // qgd_k_tiny.hip for calls that return only [grad | scalars] (StoredSweep: SWEEP_SMALL).  QGD_TINY=0 /
+    // qgd_set_small_path(h, 0): off.  The fused front (qgd_device.h: qgdk_ctx::front) takes full evaluations of
+    // qgd_eval_forward / qgd_discrete_adjoint on problems qgdk_front_supported admits (SWEEP_FRONT).
     bool small_path = !(getenv("QGD_TINY") && atoi(getenv("QGD_TINY")) == 0);
-    bool history_stale = false;
-    // The fused front (qgd_device.h: qgdk_ctx::front) takes full evaluations of qgd_eval_forward / qgd_discrete_adjoint on problems
-    // qgdk_front_supported admits.  front_last: the device buffers hold such an evaluation -- state history, lambda and forcing
-    // are the same quantities as ever, but L / R / Linv / P are the same-point form's: an entry point that wants the two-point
-    // form's (qgd_get_intermediate) redoes the forward evaluation on the general path first.
-    bool front_last = false;
-    std::vector<double> tiny_pcof;      // pcof of the last small-path evaluation
-    bool tiny_was_gradient = false;
     bool mirror_off = (getenv("QGD_RESULT_MIRROR") && atoi(getenv("QGD_RESULT_MIRROR")) == 0);
     // the launch sequence of one full gradient evaluation as a hipGraph, opt-in (QGD_GRAPH=1).  Measured: no gain
     // on cnot3 (420 us either way) and 5 % on cnot2 (98 vs 104 us) -- an evaluation is a chain of ~15 DEPENDENT
@@ -104,7 +131,6 @@ struct qgd_handle_s {
     hipStream_t copy_stream = nullptr;
     hipStream_t copy_stream2 = nullptr;   // the second half of a large pinned download goes to a second DMA engine 
     hipEvent_t ev_ready = nullptr;
-    std::vector<double> fwd_pcof;       // the pcof of the forward sweep that is on the device (history_precomputed)
     std::vector<double> scatter_tmp;    // unregistered lambda_history: compact copy, scattered on the host
     bool copies_pending = false;
     bool forcing_zero = false;          // no guard projector: the adjoint forcing is all zeros and nothing has written it since
@@ -207,11 +233,37 @@ struct PhaseTimer {
 };
 
 
-// The scan layout of one window of `S_w` steps: B blocks of blen steps (+ the second level for B > 8).
-// A history of the GENERAL path is about to be produced, or the stored one is void: whatever the small-problem path left behind
-// (history_stale: "the device buffers hold no history of the last evaluation"; tiny_pcof: the pcof to redo it from) no longer
-// describes the handle.
-inline void general_history(qgd_handle h) { h->history_stale = false; h->tiny_pcof.clear(); }
+// The transitions of the StoredSweep record (described at its declaration).
+inline void sweep_void(qgd_handle h) { h->sweep.kind = SWEEP_NONE; h->sweep.derivs = false; }
+
+// a forward sweep is about to overwrite the buffers (after the checks that can refuse the call, before the first launch)
+inline void sweep_begin(qgd_handle h) { sweep_void(h); h->sweep.front = false; }
+
+inline void sweep_done(qgd_handle h, SweepKind kind, const double *pcof, int n_pcof, bool gradient = false)
+{
+    StoredSweep &s = h->sweep;
+    s.kind = kind;
+    s.has_pcof = pcof != nullptr;
+    if (pcof) s.pcof.assign(pcof, pcof + n_pcof); else s.pcof.clear();
+    s.gradient = gradient;
+    s.reusable = true;
+    s.derivs = false;
+    s.front = kind == SWEEP_FRONT;
+}
+
+// a new target or cost type
+inline void sweep_terminal_changed(qgd_handle h) { if (h->sweep.kind == SWEEP_FRONT) h->sweep.reusable = false; }
+
+// the buffers hold a forward sweep that an adjoint sweep can differentiate
+inline bool sweep_stored(qgd_handle h) { return h->sweep.kind == SWEEP_GENERAL || h->sweep.kind == SWEEP_FRONT; }
+
+// may a history_precomputed call with this pcof skip the forward sweep?
+inline bool sweep_reusable(qgd_handle h, const double *pcof, int n_pcof)
+{
+    const StoredSweep &s = h->sweep;
+    if (!sweep_stored(h) || !s.reusable || s.has_pcof != (pcof != nullptr)) return false;
+    return !pcof || (n_pcof > 0 && (size_t)n_pcof == s.pcof.size() && !memcmp(pcof, s.pcof.data(), sizeof(double) * n_pcof));
+}
 
 
 // (QGD_CREATE_DEFER_GRID) entry points that read or size anything by the time grid allocate it first
@@ -312,10 +364,6 @@ int comm_wait(qgd_handle h);
 int comm_collective(qgd_handle h, int which);
 const double *comm_result(qgd_handle h);
 
-// qgd_host_eval.cpp
-bool same_pcof(qgd_handle h, const double *pcof, int n_pcof);
-
-// qgd_host_comm.cpp
 int comm_forward(qgd_handle h, const double *pcof, int n_pcof);
 int comm_discrete_adjoint(qgd_handle h, const double *pcof, int n_pcof, int history_precomputed, double *grad, double *uv_history, double *lambda_history, double *adjoint_forcing, double *out3);
 int comm_discrete_adjoint_body(qgd_handle h, const double *pcof, int n_pcof, int history_precomputed, double *grad, double *uv_history, double *lambda_history, double *adjoint_forcing, double *out3);

@@ -246,7 +246,8 @@ int alloc_grid(qgd_handle h)
     }
     HIP_TRY(h, hipMemcpyAsync(k.cw, k.cw_host, sizeof(double) * 2 * (k.m + 1), hipMemcpyHostToDevice, k.stream));
     HIP_TRY(h, hipStreamSynchronize(k.stream));
-    h->have_basis = h->have_tables = h->forward_valid = h->derivs_valid = false;
+    h->have_basis = h->have_tables = false;
+    sweep_void(h);
     h->tab_p_host.clear(); h->tab_q_host.clear();
     free_pool(h->basis_bufs);
     k.scal = h->scal_static; k.grad = nullptr; k.redbuf = nullptr; if (h->status_static) k.status = h->status_static;
@@ -559,9 +560,7 @@ int qgd_set_target(qgd_handle h, const double *target_real)
     HIP_TRY(h, hipMemcpy(k.target, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
     h->target_host.assign(target_real, target_real + (size_t)2 * k.N * k.c);
     k.have_target = 1;
-    // (a stored forward sweep of the fused front carries L_N^-H target with it: a history_precomputed call after a new target
-    //  redoes the sweep instead of reusing it)
-    if (h->front_last) h->fwd_pcof.clear();
+    sweep_terminal_changed(h);
     return QGD_OK;
 }
 
@@ -573,8 +572,8 @@ int qgd_set_cost_type(qgd_handle h, int32_t cost_type)
         return fail(h, QGD_ERR_ARGUMENT, "Invalid cost type (0 :Infidelity, 1 :Tracking, 2 :Norm)");    // the reference throws "Invalid cost type"
     if (h->k.cost_type == cost_type) return QGD_OK;      // (a shim that sets it on every call must not cost a captured graph)
     drop_graph(h);
-    h->k.cost_type = cost_type;     // (a stored forward sweep stays valid: history_precomputed re-forms the terminal condition)
-    if (h->front_last) h->fwd_pcof.clear();      // (... unless it is the fused front's, whose k_psi formed the terminal value of the OLD cost type: the sweep is redone)
+    h->k.cost_type = cost_type;
+    sweep_terminal_changed(h);
     return QGD_OK;
 }
 
@@ -588,7 +587,8 @@ int qgd_set_control_basis(qgd_handle h, const int32_t *n_coeff, const double *co
     qgdk_ctx &k = h->k;
     free_pool(h->basis_bufs);
     free_pool(h->forced_bufs); h->forced_key = 0;
-    h->have_basis = false; h->forward_valid = false; general_history(h); h->derivs_valid = false; h->fwd_pcof.clear();
+    h->have_basis = false;
+    sweep_void(h); h->sweep.has_pcof = false;
     k.scal = h->scal_static; k.grad = nullptr; k.redbuf = nullptr; if (h->status_static) k.status = h->status_static;
     h->ncoef.assign(k.n_ops, 0); h->poff.assign(k.n_ops, 0); h->goff.assign(k.n_ops, 0);
     size_t total = 0; int np = 0, ncmax = 0;
@@ -673,7 +673,8 @@ int qgd_set_control_tables(qgd_handle h, const double *pt, const double *qt)
     if (h->chunks_eff > 1) {      // a windowed grid: the tables of the whole grid stay on the host, each window uploads its slice
         const size_t all = (size_t)k.nt_glob * (k.m + 1) * k.n_ops;
         h->tab_p_host.assign(pt, pt + all); h->tab_q_host.assign(qt, qt + all);
-        h->have_tables = true; h->forward_valid = false; general_history(h);
+        h->have_tables = true;
+        sweep_void(h);
         return QGD_OK;
     }
     h->tab_p_host.clear(); h->tab_q_host.clear();
@@ -773,7 +774,7 @@ int qgd_set_operator_path(qgd_handle h, int32_t mode)
     if (mode == 2 && !h->sparse_available)
         return fail(h, QGD_ERR_UNSUPPORTED, "the operators are too dense (or N > 64) for the sparse kernels");
     h->k.use_sparse = (mode == 2) || (mode == 0 && h->sparse_available && !qgd_path("dense_ops"));
-    h->forward_valid = false; general_history(h); h->derivs_valid = false;
+    sweep_void(h);
     return QGD_OK;
 }
 

@@ -164,7 +164,7 @@ int comm_forward(qgd_handle h, const double *pcof, int n_pcof)
         if ((rc = forward_begin(h, pcof, n_pcof))) return rc;
         if ((rc = forward_end(h))) return rc;
     }
-    if (pcof) h->fwd_pcof.assign(pcof, pcof + n_pcof); else h->fwd_pcof.clear();
+    sweep_done(h, SWEEP_GENERAL, pcof, n_pcof);
     return QGD_OK;
 }
 
@@ -181,7 +181,7 @@ int comm_discrete_adjoint(qgd_handle h, const double *pcof, int n_pcof, int hist
     // what every rank gets alike is refused before anything is launched (no collective is left half-entered)
     if (pcof && n_pcof != h->k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
     if (!pcof && !h->have_tables && h->k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
-    if (history_precomputed && !h->forward_valid) return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+    if (history_precomputed && h->sweep.kind == SWEEP_NONE) return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
     return comm_local_error(h, comm_discrete_adjoint_body(h, pcof, n_pcof, history_precomputed, grad, uv_history, lambda_history, adjoint_forcing, out3));
 }
 
@@ -192,9 +192,7 @@ int comm_discrete_adjoint_body(qgd_handle h, const double *pcof, int n_pcof, int
     qgdk_ctx &k = h->k;
     int rc;
     struct CopyGuard { qgd_handle h; ~CopyGuard() { (void)finish_copies(h); h->defer_terminal = false; h->lambda_out = nullptr; } } guard{h};
-    if (history_precomputed && !h->forward_valid)
-        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
-    const bool reuse = history_precomputed && same_pcof(h, pcof, n_pcof);
+    const bool reuse = history_precomputed && sweep_reusable(h, pcof, n_pcof);
     const bool time = h->comm_shard == QGD_SHARD_TIME;
     if (reuse) {
         // time shards: the rank's own guard sum is still in scal (the reductions are out of place); column shards: the
@@ -210,7 +208,7 @@ int comm_discrete_adjoint_body(qgd_handle h, const double *pcof, int n_pcof, int
     if (!time) { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal_given(&k)); }
     if (adjoint_forcing && (rc = copy_panels_out(h, k.forcing, &h->stage_f, adjoint_forcing, 1, 0))) return rc;
     if (uv_history) {
-        if (!h->derivs_valid) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->derivs_valid = true; }
+        if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
         if ((rc = copy_history_out(h, uv_history))) return rc;
     }
     if ((rc = adjoint_begin(h))) return rc;
@@ -244,7 +242,7 @@ int comm_eval_forward_body(qgd_handle h, const double *pcof, int n_pcof, double 
     if (rc) return rc;
     if (uv_history) {
         { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
-        h->derivs_valid = true;
+        h->sweep.derivs = true;
         if ((rc = copy_history_out(h, uv_history, h->save_every))) return rc;
     }
     K_TRY(h, qgdk_flag_to_scal(&k));      // a singular step matrix on ANY rank fails the call on every rank

@@ -150,7 +150,6 @@ int copy_lambda_full_out(qgd_handle h, double *out)
 
 int upload_pcof(qgd_handle h, const double *pcof, int n_pcof)
 {
-    if (n_pcof != h->k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
     const double *src = pcof;
     if (h->host_in && h->host_out_len >= (size_t)n_pcof) {   // every evaluation ends with a stream synchronisation: the buffer is free
         memcpy(h->host_in, pcof, sizeof(double) * n_pcof);
@@ -185,8 +184,11 @@ int forward_begin(qgd_handle h, const double *pcof, int n_pcof, bool allow_front
 {
     qgdk_ctx &k = h->k;
     if (h->stream_dead) return fail(h, QGD_ERR_COMM, "a communicator of this handle was leaked with a collective stuck on its stream: the handle accepts no further evaluation");
+    if (pcof && !h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before passing pcof");
+    if (pcof && n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
+    if (!pcof && !h->have_tables && k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
     k.front = (allow_front && front_applies(h, pcof, n_pcof)) ? 1 : 0;
-    h->front_last = k.front != 0;
+    sweep_begin(h);
     // guard penalty: the guard stage stores its workgroups' partial sums and a later stage adds them in a fixed order (the
     // same bits on every run)
     k.gpart_on = k.gpart ? 1 : 0;
@@ -195,19 +197,16 @@ int forward_begin(qgd_handle h, const double *pcof, int n_pcof, bool allow_front
     // resident and the final time its own); a window of a long grid and the other ranks of a partition launch k_guard_fold
     k.gpart_terminal = (h->chunks_eff == 1 && k.part_rank == k.part_world - 1) ? 1 : 0;
     if (pcof) {
-        if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before passing pcof");
         PhaseTimer t(h, "tables");
         if (k.front) {
             K_TRY(h, qgdk_tables_front(&k, pcof, n_pcof));      // tables + the step matrices k_front's workgroups past two per CU start from + phi_0
-        } else if (n_pcof == k.n_pcof && n_pcof <= QGD_PCOF_KERNARG && h->graph_off && !qgd_path("pcof_copy")) {   // (a captured graph would freeze the values)
+        } else if (n_pcof <= QGD_PCOF_KERNARG && h->graph_off && !qgd_path("pcof_copy")) {   // (a captured graph would freeze the values)
             K_TRY(h, qgdk_tables_kernarg(&k, pcof, n_pcof));      // pcof rides in the kernel arguments: no copy packet
         } else {
             int rc = upload_pcof(h, pcof, n_pcof);
             if (rc) return rc;
             K_TRY(h, qgdk_tables(&k, h->pcof_dev));
         }
-    } else if (!h->have_tables && k.n_ops > 0) {
-        return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
     }
     if (!pcof) {   // (with pcof, k_tables clears them)
         if (!k.keep_scal) HIP_TRY(h, hipMemsetAsync(k.scal, 0, 4 * sizeof(double), k.stream));      // (a later window of a long grid keeps the running guard sum)
@@ -223,8 +222,6 @@ int forward_begin(qgd_handle h, const double *pcof, int n_pcof, bool allow_front
         else { PhaseTimer t(h, "propagator"); K_TRY(h, qgdk_propagator(&k)); }
         { PhaseTimer t(h, "sweep_forward"); K_TRY(h, qgdk_forward_blocks(&k)); }
     }
-    h->forward_valid = false; general_history(h);
-    h->derivs_valid = false;
     h->status_dirty = true;       // (a general-path evaluation can leave the status word set without its result passing through fail():
                                   //  qgd_cols_forward, qgd_dist_* without qgd_dist_finish -- the small-problem path clears it from the host)
     return QGD_OK;
@@ -254,7 +251,6 @@ int forward_end(qgd_handle h)
         PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target));
     }
     if (k.gpart_on && !k.gpart_terminal && k.have_guard) { PhaseTimer t(h, "guard"); K_TRY(h, qgdk_guard_fold(&k)); }
-    h->forward_valid = true;
     return QGD_OK;
 }
 
@@ -280,7 +276,7 @@ int adjoint_end(qgd_handle h)
         int rc = h->lambda_derivs ? copy_lambda_full_out(h, out) : copy_panels_out(h, k.lam, &h->stage_lam, out, (size_t)k.m + 1, 1);
         if (rc) return rc;
     }
-    if (!h->derivs_valid && qgdk_gradient_needs_derivs(&k)) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->derivs_valid = true; }
+    if (!h->sweep.derivs && qgdk_gradient_needs_derivs(&k)) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
     { PhaseTimer t(h, "gradient"); K_TRY(h, qgdk_gradient(&k)); }
     return QGD_OK;
 }
@@ -293,8 +289,7 @@ int run_forward(qgd_handle h, const double *pcof, int n_pcof, bool allow_front)
     int rc = forward_begin(h, pcof, n_pcof, allow_front);
     if (rc) return rc;
     if ((rc = forward_end(h))) return rc;
-    if (pcof) h->fwd_pcof.assign(pcof, pcof + n_pcof); else h->fwd_pcof.clear();
-    h->history_stale = false;
+    sweep_done(h, h->k.front ? SWEEP_FRONT : SWEEP_GENERAL, pcof, n_pcof);
     return QGD_OK;
 }
 
@@ -323,9 +318,8 @@ int tiny_evaluate(qgd_handle h, const double *pcof, int n_pcof, bool gradient, d
     k.mirror_dev = nullptr;
     if (e) return fail(h, QGD_ERR_NO_DEVICE, std::string("small-problem evaluation failed to launch: ") + hipGetErrorString((hipError_t)e));
     h->mirror_armed = mirror;
-    h->forward_valid = true; h->derivs_valid = false; h->history_stale = true; h->forcing_zero = false;
-    h->fwd_pcof.clear();
-    h->tiny_pcof.assign(pcof, pcof + n_pcof); h->tiny_was_gradient = gradient;
+    h->forcing_zero = false;
+    sweep_done(h, SWEEP_SMALL, pcof, n_pcof, gradient);
     return fetch_results(h, gradient ? grad : nullptr, out3, nullptr);
 }
 
@@ -406,13 +400,6 @@ int fetch_results(qgd_handle h, double *grad, double *out3, const double *src)
 }
 
 
-bool same_pcof(qgd_handle h, const double *pcof, int n_pcof)
-{
-    if (h->history_stale) return false;     // (the last evaluation ran on the small-problem path: no stored history to reuse)
-    return pcof ? ((size_t)n_pcof == h->fwd_pcof.size() && n_pcof > 0 && !memcmp(pcof, h->fwd_pcof.data(), sizeof(double) * n_pcof))
-                : h->fwd_pcof.empty();
-}
-
 }  // namespace qgdh
 
 using namespace qgdh;
@@ -436,7 +423,7 @@ int qgd_eval_forward(qgd_handle h, const double *pcof, int32_t n_pcof, double *u
     if (rc) return rc;
     if (uv_history) {
         { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
-        h->derivs_valid = true;
+        h->sweep.derivs = true;
     }
     if (uv_history && (rc = copy_history_out(h, uv_history, h->save_every))) return rc;
     if ((rc = fetch_results(h, nullptr, out3))) { (void)finish_copies(h); return rc; }
@@ -458,14 +445,14 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, int32
     if (h->part_world != 1) return fail(h, QGD_ERR_STATE, "partitioned handle: use the qgd_dist_* entry points, or give the handle a communicator (qgd_comm_init_rccl)");
     int rc;
     if (h->chunks_eff > 1) {      // bounded-memory time grid: forward pass over the windows, adjoint pass back over them
-        if (history_precomputed && !h->forward_valid) return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+        if (history_precomputed && h->sweep.kind == SWEEP_NONE) return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
         // (uv_history is an output: a reused forward pass would have nothing to copy it from, so the pass is redone)
-        if ((uv_history || !(history_precomputed && same_pcof(h, pcof, n_pcof))) && (rc = chunked_forward(h, pcof, n_pcof, uv_history))) return rc;
+        if ((uv_history || !(history_precomputed && sweep_reusable(h, pcof, n_pcof))) && (rc = chunked_forward(h, pcof, n_pcof, uv_history))) return rc;
         if ((rc = chunked_adjoint(h, lambda_history, adjoint_forcing))) return rc;
         return fetch_results(h, grad, out3);
     }
     if (!uv_history && !lambda_history && !adjoint_forcing && tiny_applies(h, pcof, n_pcof)) {
-        if (history_precomputed && !h->forward_valid) return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+        if (history_precomputed && h->sweep.kind == SWEEP_NONE) return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
         return tiny_evaluate(h, pcof, n_pcof, true, grad, out3);      // (four launches redo the sweep faster than the stored one could be reused)
     }
     // full evaluation, nothing but [grad | scalars] coming back, no event bracketing: replay the captured launch sequence
@@ -496,9 +483,8 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, int32
             memcpy(h->host_in, pcof, sizeof(double) * n_pcof);
             HIP_TRY(h, hipGraphLaunch(h->graph_exec, k.stream));
             HIP_TRY(h, hipStreamSynchronize(k.stream));
-            h->forward_valid = true; general_history(h);
-            h->fwd_pcof.assign(pcof, pcof + n_pcof);
-            h->derivs_valid = qgdk_gradient_needs_derivs(&k) != 0;
+            sweep_done(h, SWEEP_GENERAL, pcof, n_pcof);
+            h->sweep.derivs = qgdk_gradient_needs_derivs(&k) != 0;
             const size_t np = (size_t)k.n_pcof;
             int st;
             memcpy(&st, h->host_out + np + 4, sizeof(int));
@@ -512,9 +498,9 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, int32
     // history_precomputed: the reference differentiates the history it is GIVEN with the pcof it is given
     // (eval_grad_discrete_adjoint.jl:118-124).  The device keeps its own copy of the last forward sweep; it is
     // reused only when it was computed from this very pcof, otherwise the sweep is simply redone.
-    if (history_precomputed && !h->forward_valid)
+    if (history_precomputed && h->sweep.kind == SWEEP_NONE)
         return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
-    const bool reuse = history_precomputed && same_pcof(h, pcof, n_pcof);
+    const bool reuse = history_precomputed && sweep_reusable(h, pcof, n_pcof);
     if (reuse) {
         // the terminal right-hand side may not have been written if the target was set later
         { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, 1)); }
@@ -528,7 +514,7 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, int32
     // keeps the link busy while the stage derivatives of the state history are still being computed and laid out
     if (adjoint_forcing && (rc = copy_panels_out(h, k.forcing, &h->stage_f, adjoint_forcing, 1, 0))) return rc;
     if (uv_history) {
-        if (!h->derivs_valid) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->derivs_valid = true; }
+        if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
         if ((rc = copy_history_out(h, uv_history))) return rc;
     }
     if ((rc = adjoint_begin(h))) return rc;
@@ -569,11 +555,9 @@ int qgd_eval_forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, co
     k.gpart_n = k.nt;
     { PhaseTimer t(h, "guard"); K_TRY(h, qgdk_guard_kernel(&k)); }
     { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target)); }
-    h->forward_valid = false; general_history(h);      // this history is not the one the adjoint sweep differentiates
     if (uv_history) {
         { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
         K_TRY(h, qgdk_forcing_add_derivs(&k));     // w_j = D_j w_0 + E_j
-        h->derivs_valid = false;
     }
     if (uv_history && (rc = copy_history_out(h, uv_history, h->save_every))) return rc;
     if ((rc = fetch_results(h, nullptr, out3))) { (void)finish_copies(h); return rc; }
@@ -622,7 +606,7 @@ int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, doubl
     const size_t cpS = (size_t)k.n_pcof * k.cp, hstepS = (size_t)k.Np * 2 * cpS;
     size_t nt = k.nt, B = k.scan_blocks;
     if (h->chunks_eff == 1) {
-        if (!h->derivs_valid) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->derivs_valid = true; }
+        if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
         if ((rc = forced_buffers(h, nt, B))) return rc;
         HIP_TRY(h, hipMemsetAsync(k.fs_bnd, 0, hstepS * sizeof(double), k.stream));
         HIP_TRY(h, hipMemsetAsync(k.fs_gacc, 0, ((size_t)k.n_pcof + 1) * sizeof(double), k.stream));
@@ -632,11 +616,9 @@ int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, doubl
         // Windows in order: each forms its matrices and forward history again from its stored start state (as the adjoint pass
         // does), the sensitivities of all parameters continue from where the previous window left them, the guard part of the
         // gradient accumulates.  (eval_grad_forced.jl:17-194 keeps no matrices either: one forced sweep per parameter.)
-        const std::vector<double> pc(h->fwd_pcof);
-        const double *pp = pc.empty() ? nullptr : pc.data();
         size_t nt0 = 0, B0 = 0;
         for (int r = 0; r < h->chunks_eff; r++) {
-            if ((rc = chunk_forward(h, pp, (int)pc.size(), r, true))) return rc;
+            if ((rc = chunk_forward(h, pcof, n_pcof, r, true))) return rc;
             if (r == 0) {
                 nt0 = (size_t)k.nt; B0 = (size_t)k.scan_blocks;      // (the first window is the longest)
                 if ((rc = forced_buffers(h, nt0, B0))) return rc;
@@ -651,7 +633,6 @@ int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, doubl
             if (r + 1 < h->chunks_eff)      // s at the start of the next window
                 HIP_TRY(h, hipMemcpyAsync(k.fs_bnd, k.fs_bnd + B * hstepS, hstepS * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
         }
-        h->derivs_valid = false;
     }
     if ((rc = check_status(h))) return rc;
     std::vector<double> sN(hstepS), gacc(k.n_pcof), scal(4), wN;
@@ -730,7 +711,6 @@ int qgd_eval_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, const dou
         HIP_TRY(h, hipMemcpyAsync(k.lam + (nt - 1) * hstep, lamN.data(), hstep * sizeof(double), hipMemcpyHostToDevice, k.stream));
         rc = copy_lambda_full_out(h, lambda_history);
         const int rc2 = finish_copies(h);
-        h->forward_valid = false; general_history(h);
         return rc ? rc : rc2;
     }
     std::vector<double> l(nt * hstep);
@@ -744,7 +724,6 @@ int qgd_eval_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, const dou
             dst[i] = src[o]; dst[N + i] = src[o + 8];
         }
     }
-    h->forward_valid = false; general_history(h);   // the state history was not computed
     return QGD_OK;
 }
 
@@ -803,8 +782,8 @@ int qgd_get_intermediate(qgd_handle h, const char *name, double *out, size_t cap
     if (needed) *needed = need;
     if (!out) return QGD_OK;
     if (capacity < need) return fail(h, QGD_ERR_ARGUMENT, "buffer too small");
-    if (s == "small_path") { out[0] = h->history_stale ? 1.0 : 0.0; return QGD_OK; }
-    if (s == "front_path") { out[0] = h->front_last ? 1.0 : 0.0; return QGD_OK; }         // did the LAST forward evaluation take the fused front      // did the LAST evaluation run on the small-problem path
+    if (s == "small_path") { out[0] = h->sweep.kind == SWEEP_SMALL ? 1.0 : 0.0; return QGD_OK; }
+    if (s == "front_path") { out[0] = h->sweep.front ? 1.0 : 0.0; return QGD_OK; }
     if (s == "selection") {      // which kernel families this problem runs on (tests assert that a shape selects what it is meant to)
         out[0] = k.use_sparse ? 2.0 : (k.dense_gemm ? 1.0 : 0.0);      // 2 sparse (ELL), 1 N > 64 GEMM-style kernels, 0 dense N <= 64
         out[1] = (k.dense_gemm && !k.use_sparse) ? (double)qgdk_dense_sigma_form(&k) : -1.0;
@@ -814,19 +793,14 @@ int qgd_get_intermediate(qgd_handle h, const char *name, double *out, size_t cap
     }
     NEEDS_RESIDENT_GRID(h, "qgd_get_intermediate");
     if (h->stream_dead) return fail(h, QGD_ERR_COMM, "a communicator of this handle was leaked with a collective stuck on its stream");
-    if (h->history_stale && s != "repivoted" && !h->tiny_pcof.empty()) {
-        // the last evaluation ran on the small-problem path, which keeps no intermediates: the same evaluation once more on
-        // the general path (diagnostics only)
-        const std::vector<double> pc = h->tiny_pcof;
+    const bool matrices = s == "L" || s == "R" || s == "Linv" || s == "P";
+    if ((h->sweep.kind == SWEEP_SMALL && s != "repivoted") || (h->sweep.front && h->sweep.has_pcof && matrices)) {
+        // the small-problem path keeps no intermediates, the front's step matrices are the same-point form's (L^H, R^H, L^-H,
+        // S): the evaluation once more on the general path (diagnostics only; the copy: run_forward records its pcof)
+        const std::vector<double> pc = h->sweep.pcof;
+        const bool adjoint = h->sweep.kind == SWEEP_SMALL && h->sweep.gradient && k.have_target;
         int rcs = run_forward(h, pc.data(), (int)pc.size());
-        if (!rcs && h->tiny_was_gradient && k.have_target) { rcs = adjoint_begin(h); if (!rcs) rcs = adjoint_end(h); }
-        if (rcs) return rcs;
-    }
-    if (h->front_last && (s == "L" || s == "R" || s == "Linv" || s == "P") && !h->fwd_pcof.empty()) {
-        // the last evaluation took the fused front, whose step matrices are the same-point form's (L^H, R^H, L^-H, S): the
-        // forward evaluation once more on the general path (diagnostics only)
-        const std::vector<double> pc = h->fwd_pcof;
-        const int rcs = run_forward(h, pc.data(), (int)pc.size(), false);
+        if (!rcs && adjoint) { rcs = adjoint_begin(h); if (!rcs) rcs = adjoint_end(h); }
         if (rcs) return rcs;
     }
     HIP_TRY(h, hipStreamSynchronize(k.stream));
@@ -910,7 +884,9 @@ int qgd_dist_forward_end(qgd_handle h)
 {
     if (!h) return QGD_ERR_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    return forward_end(h);
+    const int rc = forward_end(h);
+    if (!rc) sweep_done(h, SWEEP_GENERAL, nullptr, 0);      // (no pcof: a partitioned handle never reuses its sweep, qgd_discrete_adjoint refuses it)
+    return rc;
 }
 
 
@@ -919,7 +895,7 @@ int qgd_dist_adjoint_begin(qgd_handle h)
     if (!h) return QGD_ERR_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
     if (!h->k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called first");
-    if (!h->forward_valid || h->history_stale) return fail(h, QGD_ERR_STATE, "no forward evaluation to differentiate (qgd_dist_forward_* first)");
+    if (!sweep_stored(h)) return fail(h, QGD_ERR_STATE, "no forward evaluation to differentiate (qgd_dist_forward_* first)");
     return adjoint_begin(h);
 }
 
@@ -964,7 +940,7 @@ int qgd_cols_adjoint(qgd_handle h, int32_t keep_scalars)
     if (!h) return QGD_ERR_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
     qgdk_ctx &k = h->k;
-    if (!h->forward_valid || h->history_stale) return fail(h, QGD_ERR_STATE, "no forward evaluation to differentiate (qgd_cols_forward first)");
+    if (!sweep_stored(h)) return fail(h, QGD_ERR_STATE, "no forward evaluation to differentiate (qgd_cols_forward first)");
     { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal_given(&k)); }      // y_N from the all-reduced overlaps
     int rc;
     if ((rc = adjoint_begin(h))) return rc;

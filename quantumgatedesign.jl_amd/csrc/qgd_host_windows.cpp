@@ -161,8 +161,7 @@ int chunked_forward(qgd_handle h, const double *pcof, int n_pcof, double *uv_his
         }
     }
     { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target)); }      // overlaps (and y_N) from the final state
-    h->forward_valid = true; h->derivs_valid = false;
-    if (pcof) h->fwd_pcof.assign(pcof, pcof + n_pcof); else h->fwd_pcof.clear();
+    sweep_done(h, SWEEP_GENERAL, pcof, n_pcof);
     return QGD_OK;
 }
 
@@ -172,12 +171,13 @@ int chunked_adjoint(qgd_handle h, double *lambda_history, double *adjoint_forcin
     qgdk_ctx &k = h->k;
     const size_t hstep = (size_t)k.Np * 2 * k.cp;
     const int W = h->chunks_eff;
+    const StoredSweep kept = h->sweep;      // (the window re-runs below leave the window-boundary states of this sweep as they are)
     int rc;
     if (lambda_history)      // (the library writes the j = 0 columns; the others, and time index 0, are zero as in the resident call)
         memset(lambda_history, 0, sizeof(double) * 2 * (size_t)k.N * (k.m + 1) * (size_t)k.nt_glob * k.c);
     for (int r = W - 1; r >= 0; r--) {
         if (h->resident_window != r) {
-            if ((rc = chunk_forward(h, h->fwd_pcof.empty() ? nullptr : h->fwd_pcof.data(), (int)h->fwd_pcof.size(), r, true))) return rc;
+            if ((rc = chunk_forward(h, kept.has_pcof ? kept.pcof.data() : nullptr, (int)kept.pcof.size(), r, true))) return rc;
         } else if ((rc = plan_windows(h, h->chunks_req, r))) return rc;
         if (adjoint_forcing && (rc = window_panels_out(h, k.forcing, &h->stage_f, adjoint_forcing, 1, 0))) return rc;
         if (r == W - 1) { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, 1)); }
@@ -185,7 +185,7 @@ int chunked_adjoint(qgd_handle h, double *lambda_history, double *adjoint_forcin
             for (double *dst : {k.yhist + (size_t)(k.nt - 1) * hstep, k.bndY + (size_t)k.scan_blocks * hstep, k.bndY2 + (size_t)k.scan_blocks2 * hstep})
                 HIP_TRY(h, hipMemcpyAsync(dst, h->carry_y, hstep * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
         k.grad_accumulate = (r != W - 1) ? 1 : 0;
-        h->derivs_valid = false;
+        h->sweep.derivs = false;
         rc = adjoint_begin(h);
         if (!rc) rc = adjoint_end(h);
         k.grad_accumulate = 0;
@@ -194,7 +194,7 @@ int chunked_adjoint(qgd_handle h, double *lambda_history, double *adjoint_forcin
                                                      : window_panels_out(h, k.lam, &h->stage_lam, lambda_history, (size_t)k.m + 1, 1))) return rc;
         HIP_TRY(h, hipMemcpyAsync(h->carry_y, k.yhist, hstep * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
     }
-    h->forward_valid = true;          // (the window-boundary states of this pcof are still there for history_precomputed)
+    h->sweep = kept;
     return QGD_OK;
 }
 
@@ -218,7 +218,7 @@ int chunked_eval_adjoint(qgd_handle h, const double *pcof, int n_pcof, const dou
             lamN[o + 8] = terminal_condition[N + i + n2 * col];
         }
     memset(lambda_history, 0, sizeof(double) * n2 * (m + 1) * ntg * k.c);
-    h->forward_valid = false; general_history(h); h->resident_window = -1;      // (the buffers will hold no window's forward history)
+    sweep_void(h); h->resident_window = -1;      // (the buffers will hold no window's forward history)
     int rc;
     for (int r = W - 1; r >= 0; r--) {
         if ((rc = plan_windows(h, h->chunks_req, r))) return rc;
@@ -319,7 +319,7 @@ int chunked_forward_forced(qgd_handle h, const double *pcof, int n_pcof, const d
     if (!pcof && !h->have_tables && k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
     const size_t hstep = (size_t)k.Np * 2 * k.cp;
     int rc;
-    h->forward_valid = false; general_history(h); h->resident_window = -1;       // (the window-boundary states are those of the FORCED sweep from here on)
+    sweep_void(h); h->resident_window = -1;       // (the window-boundary states are those of the FORCED sweep from here on)
     size_t nt0 = 0, B0 = 0;
     for (int r = 0; r < h->chunks_eff; r++) {
         if ((rc = plan_windows(h, h->chunks_req, r))) return rc;
@@ -351,8 +351,6 @@ int chunked_forward_forced(qgd_handle h, const double *pcof, int n_pcof, const d
         }
     }
     { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target)); }
-    h->derivs_valid = false;
-    h->fwd_pcof.clear();
     if ((rc = fetch_results(h, nullptr, out3, nullptr))) { (void)finish_copies(h); return rc; }
     return finish_copies(h);
 }

@@ -12,7 +12,7 @@ def lib():
     global _lib
     if _lib is None:
         # always through make: the hook writes a field of the library's handle, so it must be compiled against the very headers
-        # the library was built from (the Makefile knows the dependency; a stale copy pokes the wrong field)
+        # the library was built from (`make testhooks` rebuilds it every time; a stale copy pokes the wrong field)
         csrc = os.path.join(os.path.dirname(_HERE), "quantumgatedesign.jl_amd", "csrc")
         subprocess.check_call(["make", "-C", csrc, "libqgd_hip.so", "testhooks"], stdout=subprocess.DEVNULL)
         _lib = C.CDLL(_SO)

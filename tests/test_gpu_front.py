@@ -193,6 +193,41 @@ def test_front_eligibility_and_reuse(qgd, monkeypatch):
     dp.close()
 
 
+def test_front_sweep_after_new_target_or_cost_type(qgd, monkeypatch):
+    """A stored front sweep after qgd_set_target / qgd_set_cost_type behaves like a general one put through the same calls.
+    A NULL-pcof history_precomputed call does not reuse it: it needs control tables, which these handles never had, so both
+    handles refuse it.  The refused call leaves the handle as it was: the front handle's "L" / "P" are still redone on the
+    general path from the stored pcof (the two-point form's), and after a new target a history_precomputed call with pcof
+    gives the general path's gradient."""
+    prob, ctrl, pcof, target = cases.cnot3_case(qgd, nsteps=24, tf=24.0)
+    t2 = target[:, ::-1].copy()
+
+    def run(paths, change):
+        monkeypatch.setenv("QGD_PATHS", paths)
+        dp = qgd.DeviceProblem(prob, 8); dp.set_target(target); dp.set_controls(ctrl)
+        dp.eval_forward(pcof)
+        assert dp.front_path_taken() == (paths == "front")
+        if change == "target":
+            dp.set_target(t2)
+        else:
+            dp.set_cost_type("Tracking")
+        grad, out3 = np.zeros(dp.n_pcof), np.zeros(3)
+        rc = dp.lib.qgd_discrete_adjoint(dp.h, None, 0, 1, grad.ctypes.data, None, None, None, out3.ctypes.data)
+        assert rc == qgd._lib.QGD_ERR_STATE, (paths, change, rc)
+        assert dp.front_path_taken() == (paths == "front")
+        out = dict(L=dp.intermediate("L"), P=dp.intermediate("P"))
+        if change == "target":
+            out["g"] = dp.discrete_adjoint(pcof, history_precomputed=True)[0]
+        dp.close()
+        return out
+
+    for change in ("target", "cost_type"):
+        f, n = run("front", change), run("no_front", change)
+        assert np.abs(f["L"] - n["L"]).max() <= 1e-12 and np.abs(f["P"] - n["P"]).max() <= 1e-12, change
+        if change == "target":
+            assert np.abs(f["g"] - n["g"]).max() <= 1e-11 * np.abs(n["g"]).max()
+
+
 def test_front_non_finite_coefficients(qgd, monkeypatch):
     """A coefficient vector with a NaN / an infinity in it: the evaluation ENDS with non-finite results, and the next
     evaluation of the same handle is bit for bit what it was before."""
