@@ -366,6 +366,15 @@ int qgd_eval_forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, co
  * directly (general control path: the basis then holds the Jacobian at the current pcof).  Honours qgd_set_cost_type. */
 int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, double *grad);
 
+/* eval_hessian (src/eval_hessian.jl): the EXACT Hessian of the discrete objective (the reference forms it by finite
+ * differences).  hess[n_pcof x n_pcof] (symmetric, row-major = column-major); grad may be NULL, else it receives the
+ * forced gradient.  Honours qgd_set_cost_type.  Needs qgd_set_target and qgd_set_control_basis (else QGD_ERR_STATE) and
+ * pcof (controls linear in pcof).  A partitioned handle: QGD_ERR_STATE.  QGD_ERR_UNSUPPORTED: pcof NULL (tables set
+ * directly), a windowed time grid, N > 64, no control operators, or more than 64 basis directions 2 * n_ops * order/2.
+ * QGD_ERR_MEMORY when the sensitivity history [nsteps+1][N][2 n_pcof c] and the work buffers (kept on the handle for the
+ * next call) do not fit the memory budget or the free device memory.  DESIGN.md section 4c. */
+int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *hess, double *grad);
+
 /* Operator path of the step-matrix and gradient kernels.  mode 0: automatic (sparse when every
  * row of the assembled Hamiltonian has at most min(16, N/2) entries and N <= 64 -- the drift +
  * a_k +/- a_k^dagger operators of src/multi_qudit_systems.jl -- else dense), 1: dense fp64 MFMA

@@ -280,6 +280,21 @@ function hip_eval_grad_forced(prob::SchrodingerProb, controls, pcof::Vector{Floa
     return grad
 end
 
+# eval_hessian(prob, controls, pcof, target; order) (src/eval_hessian.jl): the exact Hessian of the discrete objective on the
+# device (controls linear in pcof), n_pcof x n_pcof.
+function hip_eval_hessian(prob::SchrodingerProb, controls, pcof::Vector{Float64},
+        target::AbstractMatrix{<:Number}; order::Int=2, cost_type=:Infidelity)
+    dp = device_problem(prob, order)
+    pc_ptr, pc_len = set_controls!(dp, prob, controls, pcof)
+    set_cost_type!(dp, cost_type)
+    tr = Matrix{Float64}(vcat(real(target), imag(target)))
+    check(dp.handle, ccall((:qgd_set_target, libqgd), Cint, (Ptr{Cvoid}, Ptr{Float64}), dp.handle, tr))
+    hess = zeros(length(pcof), length(pcof))
+    GC.@preserve pcof check(dp.handle, ccall((:qgd_eval_hessian, libqgd), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+          dp.handle, pc_ptr, pc_len, hess, C_NULL))
+    return hess
+end
+
 # ---- several GPUs: RCCL inside the library (include/qgd.h, "several GPUs behind ONE call") ------------------------------
 # One Julia process (or task pinned to a thread) per GPU.  Rank 0 makes the id; the host carries its 128 bytes to the
 # other ranks once (e.g. MPI.jl: `id = MPI.bcast(rank == 0 ? comm_unique_id() : nothing, 0, MPI.COMM_WORLD)`); after

@@ -113,6 +113,7 @@ typedef struct qgdk_ctx {
     double *fs_phi, *fs_bnd; // [B][Np][2cpS], [B+1][Np][2cpS], cpS = n_pcof * cp
     double *fs_gacc;         // [n_pcof]
     double *fs_scratch;      // per-workgroup panel slabs of k_forced_basis / k_forcing_terms when they exceed the LDS (N > 64), else null
+    double *fs_shist;        // [nt][Np][2cpS] sensitivity history written by the third scan pass (qgd_eval_hessian), else null
     // eval_forward with a user forcing: F, E [nt][m][Np][2cp]; XR, XL, Q [nt][Np][2cp]; scan buffers
     double *ff_F, *ff_E, *ff_XR, *ff_XL, *ff_Q, *ff_phi, *ff_bnd;
     int *status;
@@ -184,6 +185,11 @@ int qgdk_sparse_supported(int Np, int m, int n_ops, int Z);
 size_t qgdk_forced_lds(int Np, int m);
 int qgdk_forced_basis(const qgdk_ctx *c);
 int qgdk_forced_chains(const qgdk_ctx *c);
+// exact Hessian (qgd_k_hessian.hip)
+size_t qgdk_hess_slab(int Np, int m, int n_ops);
+int qgdk_hess_kernels(const qgdk_ctx *c, const double *shist, double *Z, double *half, double *slab, double *zt, double *Y);
+size_t qgdk_hess_gram_part(int n_pcof, int nt);
+int qgdk_hess_gram(const qgdk_ctx *c, const double *shist, double *ws, double *part, double *out);
 int qgdk_forcing_terms(const qgdk_ctx *c);
 int qgdk_forcing_add_derivs(const qgdk_ctx *c);
 int qgdk_forcing_sweep(const qgdk_ctx *c);

@@ -82,6 +82,9 @@ struct qgd_handle_s {
     std::vector<void *> static_bufs, grid_bufs, basis_bufs, forced_bufs;
     std::vector<double> target_host;   // stacked real target [2N x c] (forced gradient: the overlaps are host arithmetic)
     size_t forced_key = 0;             // (nt, n_pcof) the forced-gradient buffers were sized for
+    std::vector<void *> hess_bufs;     // qgd_eval_hessian: sensitivity history and the work buffers of qgd_k_hessian.hip
+    size_t hess_key = 0;               // (nt, n_pcof, basis directions, general guard) they were sized for
+    double *hs_shist = nullptr, *hs_ws = nullptr, *hs_Z = nullptr, *hs_half = nullptr, *hs_slab = nullptr, *hs_zt = nullptr, *hs_Y = nullptr;
     double *fsc_forced = nullptr, *fsc_forcing = nullptr;   // HBM work-panel slabs of the forced kernels when they exceed the LDS (N > 64)
     std::vector<void *> forcing_bufs;  // eval_forward with a user forcing
     size_t forcing_key = 0;

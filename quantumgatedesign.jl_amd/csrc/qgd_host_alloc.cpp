@@ -182,6 +182,7 @@ int alloc_grid(qgd_handle h)
     h->grid_ready = false;
     free_pool(h->grid_bufs);
     free_pool(h->forced_bufs); h->forced_key = 0;
+    free_pool(h->hess_bufs); h->hess_key = 0;
     free_pool(h->forcing_bufs); h->forcing_key = 0;
     free_pool(h->stage_bufs); h->stage_hist = h->stage_lam = h->stage_f = nullptr;
     h->dlam = h->dlam_scratch = h->stage_lam_full = nullptr;
@@ -522,7 +523,7 @@ void qgd_destroy(qgd_handle h)
     if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
     for (auto &r : h->regs) (void)hipHostUnregister(r.host);
     free_pool(h->stage_bufs);
-    free_pool(h->static_bufs); free_pool(h->grid_bufs); free_pool(h->basis_bufs); free_pool(h->forced_bufs); free_pool(h->forcing_bufs);
+    free_pool(h->static_bufs); free_pool(h->grid_bufs); free_pool(h->basis_bufs); free_pool(h->forced_bufs); free_pool(h->hess_bufs); free_pool(h->forcing_bufs);
     for (auto &p : h->phases) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     if (h->host_out) (void)hipHostFree(h->host_out);
     if (h->host_in) (void)hipHostFree(h->host_in);
@@ -587,6 +588,7 @@ int qgd_set_control_basis(qgd_handle h, const int32_t *n_coeff, const double *co
     qgdk_ctx &k = h->k;
     free_pool(h->basis_bufs);
     free_pool(h->forced_bufs); h->forced_key = 0;
+    free_pool(h->hess_bufs); h->hess_key = 0;
     h->have_basis = false;
     sweep_void(h); h->sweep.has_pcof = false;
     k.scal = h->scal_static; k.grad = nullptr; k.redbuf = nullptr; if (h->status_static) k.status = h->status_static;

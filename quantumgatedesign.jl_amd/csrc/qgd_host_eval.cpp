@@ -950,4 +950,117 @@ int qgd_cols_adjoint(qgd_handle h, int32_t keep_scalars)
     return QGD_OK;
 }
 
+
+// exact Hessian of the objective: the adjoint evaluation (lambda), the forced sweep with its history
+// of sensitivities kept, then the second-order contraction of qgd_k_hessian.hip.  The terminal part is host arithmetic on s_N.
+int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *hess, double *grad)
+{
+    if (h) drop_graph(h);
+    if (!h || !hess) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    NEED_GRID(h);
+    qgdk_ctx &k = h->k;
+    if (h->part_world != 1 || h->comm) return fail(h, QGD_ERR_STATE, "partitioned handle: the Hessian is single-GPU");
+    if (!k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before qgd_eval_hessian");
+    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_eval_hessian");
+    if (!pcof) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian needs pcof: with control tables set directly the second derivative of the controls is unknown");
+    if (n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
+    if (h->chunks_eff > 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian needs the whole time grid resident (this handle processes it in windows)");
+    if (k.N > 64) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian supports N <= 64");
+    if (k.n_ops < 1 || k.n_ops * 2 * k.m > 64) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian needs 1 <= 2 * n_ops * order/2 <= 64 basis directions");
+    const size_t nt = k.nt, np = (size_t)k.n_pcof, NB = (size_t)k.n_ops * 2 * k.m, gpc = (size_t)k.cp / 8;
+    const size_t hstep = (size_t)k.Np * 2 * k.cp, cpS = np * k.cp, hstepS = (size_t)k.Np * 2 * cpS;
+    const size_t n_shist = nt * hstepS, n_ws = k.have_guard == 1 ? n_shist : 0, n_Z = nt * NB * hstep, n_half = nt * gpc * NB * NB;
+    const size_t n_slab = nt * gpc * qgdk_hess_slab(k.Np, k.m, k.n_ops), n_zt = nt * NB * np;
+    const size_t n_Y = 2 * np * np + (k.have_guard ? qgdk_hess_gram_part((int)np, (int)nt) : 0);
+    const size_t key = ((nt * 1000003u + np) * 4099u + NB) * 2u + (n_ws ? 1u : 0u);
+    if (h->hess_key != key) {
+        free_pool(h->hess_bufs); h->hess_key = 0;
+        // everything this call allocates: its own buffers and, when they are not there yet, the forced gradient's (forced_buffers)
+        size_t bytes = (n_shist + n_ws + n_Z + n_half + n_slab + n_zt + n_Y) * sizeof(double);
+        const size_t fkey = (nt * 1000003u + np) * 4099u + (size_t)k.scan_blocks;
+        if (h->forced_key != fkey)
+            bytes += (2 * nt * NB * hstep + (2 * (size_t)k.scan_blocks + 1) * hstepS + np + 1) * sizeof(double);
+        size_t fr = 0, tot = 0;
+        if ((h->mem_budget && bytes > h->mem_budget) || (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr))
+            return fail(h, QGD_ERR_MEMORY, "the sensitivity history of qgd_eval_hessian does not fit (" + std::to_string(bytes) + " bytes needed)");
+        int rc;
+        if ((rc = dev_alloc(h, h->hess_bufs, &h->hs_shist, n_shist)) ||
+            (n_ws && (rc = dev_alloc(h, h->hess_bufs, &h->hs_ws, n_ws))) ||
+            (rc = dev_alloc(h, h->hess_bufs, &h->hs_Z, n_Z)) || (rc = dev_alloc(h, h->hess_bufs, &h->hs_half, n_half)) ||
+            (rc = dev_alloc(h, h->hess_bufs, &h->hs_slab, n_slab)) || (rc = dev_alloc(h, h->hess_bufs, &h->hs_zt, n_zt)) ||
+            (rc = dev_alloc(h, h->hess_bufs, &h->hs_Y, n_Y))) { free_pool(h->hess_bufs); return rc; }
+        if (!n_ws) h->hs_ws = nullptr;
+        h->hess_key = key;
+    }
+    int rc;
+    if ((rc = run_forward(h, pcof, n_pcof))) return rc;
+    if ((rc = adjoint_begin(h))) return rc;      // lambda (and the adjoint gradient, unused)
+    if ((rc = adjoint_end(h))) return rc;
+    if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
+    double *shist = h->hs_shist, *ws = h->hs_ws, *Z = h->hs_Z, *half = h->hs_half, *slab = h->hs_slab, *zt = h->hs_zt, *Y = h->hs_Y;
+    double *Gm = Y + np * np, *gpartial = Y + 2 * np * np;
+    if ((rc = forced_buffers(h, nt, k.scan_blocks))) return rc;
+    HIP_TRY(h, hipMemsetAsync(k.fs_bnd, 0, hstepS * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(k.fs_gacc, 0, (np + 1) * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(shist, 0, hstepS * sizeof(double), k.stream));      // s_0 = 0
+    HIP_TRY(h, hipMemsetAsync(Gm, 0, np * np * sizeof(double), k.stream));
+    { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); }
+    k.fs_shist = shist;
+    { PhaseTimer t(h, "forced_sweeps"); rc = qgdk_forced_chains(&k); }
+    k.fs_shist = nullptr;
+    if (rc) return fail(h, QGD_ERR_NO_DEVICE, std::string("kernel launch failed: qgdk_forced_chains: ") + hipGetErrorString((hipError_t)rc));
+    { PhaseTimer t(h, "hess_terms"); K_TRY(h, qgdk_hess_kernels(&k, shist, Z, half, slab, zt, Y)); }
+    if (k.have_guard) { PhaseTimer t(h, "hess_guard"); K_TRY(h, qgdk_hess_gram(&k, shist, ws, gpartial, Gm)); }
+    if ((rc = check_status(h))) return rc;
+    std::vector<double> sN(hstepS), gacc(np), scal(4), wN, Yh(np * np), Gh(np * np);
+    HIP_TRY(h, hipMemcpy(sN.data(), shist + (nt - 1) * hstepS, hstepS * sizeof(double), hipMemcpyDeviceToHost));
+    if (k.cost_type) {
+        wN.resize(hstep);
+        HIP_TRY(h, hipMemcpy(wN.data(), k.hist + (nt - 1) * hstep, hstep * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(h, hipMemcpy(gacc.data(), k.fs_gacc, sizeof(double) * np, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(scal.data(), k.scal, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(Yh.data(), Y, np * np * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(Gh.data(), Gm, np * np * sizeof(double), hipMemcpyDeviceToHost));
+    // terminal part: the overlaps <s_N,R>, <s_N,T> of every parameter (:Infidelity) or s_N itself (:Tracking / :Norm)
+    const size_t N = k.N, PWs = 2 * cpS;
+    const double a = scal[0], b = scal[1], f = -2.0 / ((double)k.n_ess * k.n_ess);
+    std::vector<double> sR(np), sT(np), sv(k.cost_type ? np * 2 * N * k.c : 0);
+    for (size_t p = 0; p < np; p++) {
+        double r = 0.0, t = 0.0, sW = 0.0;
+        for (int col = 0; col < k.c; col++)
+            for (size_t i = 0; i < N; i++) {
+                const size_t o = panel_index((int)i, (int)p * k.cp + col, (int)PWs);
+                const double sre = sN[o], sim = sN[o + 8];
+                const double rre = h->target_host[i + 2 * N * col], rim = h->target_host[N + i + 2 * N * col];
+                r += sre * rre + sim * rim;
+                t += sre * rim - sim * rre;
+                if (k.cost_type) {
+                    const size_t ow = panel_index((int)i, col, 2 * k.cp);
+                    const double dre = wN[ow] - (k.cost_type == QGD_COST_TRACKING ? rre : 0.0);
+                    const double dim = wN[ow + 8] - (k.cost_type == QGD_COST_TRACKING ? rim : 0.0);
+                    sW += sre * dre + sim * dim;
+                    sv[(p * k.c + col) * 2 * N + i] = sre;
+                    sv[(p * k.c + col) * 2 * N + N + i] = sim;
+                }
+            }
+        sR[p] = r; sT[p] = t;
+        if (grad) grad[p] = (k.cost_type ? sW : f * (a * r + b * t)) + gacc[p];
+    }
+    const size_t L = 2 * N * k.c;
+    for (size_t p = 0; p < np; p++)
+        for (size_t q = 0; q < np; q++) {
+            double phi;
+            if (k.cost_type) {
+                phi = 0.0;
+                for (size_t e = 0; e < L; e++) phi += sv[p * L + e] * sv[q * L + e];
+            } else {
+                phi = f * (sR[p] * sR[q] + sT[p] * sT[q]);
+            }
+            hess[p * np + q] = (Yh[p * np + q] + Yh[q * np + p]) + Gh[p * np + q] + phi;      // (Gh: both triangles from the same sums)
+        }
+    return QGD_OK;
+}
+
 }  // extern "C"

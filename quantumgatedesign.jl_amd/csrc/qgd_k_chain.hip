@@ -2066,10 +2066,11 @@ int qgdk_forced_chains(const qgdk_ctx *c)
     s2.start = c->fs_bnd; s2.start_stride = 0; s2.out = c->fs_bnd; s2.forcing = c->fs_phi; s2.nblocks = 1; s2.blen = B;
     s2.ngroups = cpS / 8; s2.fs_gpc = c->cp / 8;
     if ((rc = launch_chain<5>(s2, c->stream))) return rc;
-    if (c->have_guard) {   // (iii)
+    if (c->have_guard || c->fs_shist) {   // (iii); fs_shist: every s_n is also stored (the exact Hessian)
         ChainArgs g = f;
         g.S = c->nt - 1; g.Pmat = c->Pc; g.start = c->fs_bnd; g.start_stride = (long long)hstepS; g.nblocks = B; g.blen = c->scan_blen;
-        g.ngroups = cpS / 8; g.fs_gf = c->forcing; g.fs_gacc = c->fs_gacc;
+        g.ngroups = cpS / 8; g.out = c->fs_shist;
+        if (c->have_guard) { g.fs_gf = c->forcing; g.fs_gacc = c->fs_gacc; }
         if ((rc = launch_chain<5>(g, c->stream))) return rc;
     }
     return 0;

@@ -414,6 +414,18 @@ class DeviceProblem:
         _lib.check(self.h, self.lib.qgd_eval_grad_forced(self.h, _vp(pcof), len(pcof), _vp(grad)))
         return grad
 
+    def eval_hessian(self, pcof, grad=None):
+        """Exact Hessian of the objective at pcof, [n_pcof, n_pcof] symmetric; ``grad``: an optional
+        float64 array of n_pcof that receives the forced gradient.  Needs controls linear in pcof and the target."""
+        if getattr(self, "_general", None):
+            raise NotImplementedError("eval_hessian(method='exact') needs controls that are linear in pcof (is_linear = True)")
+        pcof = np.ascontiguousarray(pcof, dtype=np.float64)
+        hess = np.zeros((len(pcof), len(pcof)))
+        if grad is not None:
+            _check_out(grad, (len(pcof),), "grad")
+        _lib.check(self.h, self.lib.qgd_eval_hessian(self.h, _vp(pcof), len(pcof), _vp(hess), None if grad is None else _vp(grad)))
+        return hess
+
     def set_operator_path(self, mode):
         """"auto" | "dense" (fp64 MFMA kernels) | "sparse" (ELL kernels; raises if the operators do not qualify)."""
         code = {"auto": 0, "dense": 1, "sparse": 2}[mode]
@@ -545,6 +557,48 @@ def eval_grad_forced(prob, controls, pcof, target, order=2, cost_type="Infidelit
     dp.set_cost_type(cost_type)
     try:
         return dp.eval_grad_forced(pcof)
+    finally:
+        dp.set_cost_type("Infidelity")
+
+
+def eval_hessian(prob, controls, pcof, target, dpcof=1e-5, order=2, cost_type="Infidelity", method="exact"):
+    """eval_hessian(prob, controls, pcof, target; dpcof, order) (src/eval_hessian.jl).  method="exact": the exact Hessian of
+    the discrete objective on the device (controls linear in pcof).  method="finite_difference": the
+    reference's own formula -- 4-point differences of the device objective with step dpcof, n(n-1)*4 + 3n forward solves."""
+    if method not in ("exact", "finite_difference"):
+        raise ValueError("method must be 'exact' or 'finite_difference'")
+    cl = controls if isinstance(controls, (list, tuple)) else [controls]
+    if method == "exact" and not all(getattr(c, "is_linear", False) for c in cl):
+        raise NotImplementedError("eval_hessian(method='exact') needs controls that are linear in pcof (is_linear = True); "
+                                  "use method='finite_difference' for non-linear controls")
+    dp = device_problem(prob, order)
+    dp.set_controls(controls)
+    dp.set_target(target)
+    dp.set_cost_type(cost_type)
+    pcof = np.asarray(pcof, dtype=np.float64)
+    try:
+        if method == "exact":
+            return dp.eval_hessian(pcof)
+        plain = COST_TYPES[str(cost_type)] == 0
+
+        def cost(p):
+            a, b, guard = dp.eval_forward(p)
+            return (1.0 - (a * a + b * b) / prob.N_ess_levels ** 2 if plain else a) + guard
+
+        n = len(pcof)
+        hess = np.zeros((n, n))
+        f0 = cost(pcof)
+        for i in range(n):
+            for j in range(n):
+                if i != j:
+                    def at(si, sj):
+                        p = pcof.copy(); p[i] += si * dpcof; p[j] += sj * dpcof
+                        return cost(p)
+                    hess[i, j] = (at(1, 1) + at(-1, -1) - at(1, -1) - at(-1, 1)) / (4 * dpcof ** 2)
+                else:
+                    e = np.zeros(n); e[i] = dpcof
+                    hess[i, i] = (cost(pcof + e) - 2 * f0 + cost(pcof - e)) / dpcof ** 2
+        return hess
     finally:
         dp.set_cost_type("Infidelity")
 
