@@ -2,7 +2,7 @@
 // launch macros, the phase timer and the internal entry points of each unit.
 //   qgd_host_alloc.cpp    handles: creation, validation (SchrodingerProb.jl:73-154), the time grid and its windows, setters
 //   qgd_host_eval.cpp     one evaluation: forward / adjoint phases, result transport, the evaluation entry points
-//   qgd_host_windows.cpp  time grids in bounded memory: the windowed forward, adjoint and forced sweeps
+//   qgd_host_windows.cpp  time grids in bounded memory: window entry, the windowed forward and adjoint passes, their outputs
 //   qgd_host_comm.cpp     several GPUs: the RCCL binding, the collective evaluation and its failure mode
 // There is no CPU fallback: without a GPU every compute entry point fails.
 #pragma once
@@ -214,6 +214,24 @@ inline double hermite_coefficient(int j, int p, int q) { return factorial(p) * f
 
 inline size_t panel_index(int row, int col, int PWc) { return (size_t)row * PWc + (col >> 3) * 16 + (col & 7); }
 
+// A host array [2N x c] (real parts in rows 0 .. N-1, imaginary parts in rows N .. 2N-1, column stride ld) into the panel
+// layout [Np][PW] and back.
+inline void pack_panel(double *panel, int PW, const double *a, int N, int c, size_t ld)
+{
+    for (int col = 0; col < c; col++) for (int i = 0; i < N; i++) {
+        const size_t o = panel_index(i, col, PW);
+        panel[o] = a[i + ld * col]; panel[o + 8] = a[N + i + ld * col];
+    }
+}
+
+inline void unpack_panel(double *a, size_t ld, const double *panel, int PW, int N, int c)
+{
+    for (int col = 0; col < c; col++) for (int i = 0; i < N; i++) {
+        const size_t o = panel_index(i, col, PW);
+        a[i + ld * col] = panel[o]; a[N + i + ld * col] = panel[o + 8];
+    }
+}
+
 
 // One event pair per (phase, slot): the pieces of a phase that the time-chunk pipeline launches on its side streams
 // are bracketed separately (slot = chunk) and qgd_get_timings adds them up.
@@ -342,14 +360,12 @@ int adjoint_end(qgd_handle h);
 int window_history_out(qgd_handle h, double *uv_history, int save = 1);
 int window_lambda_full_out(qgd_handle h, double *out);
 int window_panels_out(qgd_handle h, const double *panels, double **stage, double *out, size_t J, int n_first);
-int window_tables(qgd_handle h);
+int enter_window(qgd_handle h, const double *pcof, int r, bool with_start_state);
 int chunk_forward(qgd_handle h, const double *pcof, int n_pcof, int r, bool rerun);
 int chunked_forward(qgd_handle h, const double *pcof, int n_pcof, double *uv_history = nullptr, int save = 1);
 int chunked_adjoint(qgd_handle h, double *lambda_history = nullptr, double *adjoint_forcing = nullptr);
-int chunked_eval_adjoint(qgd_handle h, const double *pcof, int n_pcof, const double *terminal_condition, const double *forcing, double *lambda_history);
 int forcing_buffers(qgd_handle h, size_t nt, size_t B);
 int upload_forcing(qgd_handle h, const double *forcing, size_t nt, size_t n_off);
-int chunked_forward_forced(qgd_handle h, const double *pcof, int n_pcof, const double *forcing, double *uv_history, double *out3);
 
 // qgd_host_eval.cpp
 int run_forward(qgd_handle h, const double *pcof, int n_pcof, bool allow_front = false);

@@ -553,11 +553,7 @@ int qgd_set_target(qgd_handle h, const double *target_real)
     qgdk_ctx &k = h->k;
     const size_t PWc = 2 * k.cp;
     std::vector<double> t((size_t)k.Np * PWc, 0.0);
-    for (int col = 0; col < k.c; col++) for (int i = 0; i < k.N; i++) {
-        size_t o = panel_index(i, col, (int)PWc);
-        t[o] = target_real[i + (size_t)2 * k.N * col];
-        t[o + 8] = target_real[k.N + i + (size_t)2 * k.N * col];
-    }
+    pack_panel(t.data(), (int)PWc, target_real, k.N, k.c, (size_t)2 * k.N);
     HIP_TRY(h, hipMemcpy(k.target, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
     h->target_host.assign(target_real, target_real + (size_t)2 * k.N * k.c);
     k.have_target = 1;

@@ -533,6 +533,10 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, int32
 }
 
 
+// eval_forward(...; forcing) (forward_evolution.jl:118-129,167-206).  A windowed grid runs its windows in order, each from the
+// forced state the previous one ended in, with its slice of the caller's forcing; the guard penalty accumulates over the
+// windows, the overlaps come from the final state; uv_history (stage derivatives w_j = D_j w_0 + E_j included) window by
+// window as in chunked_forward.
 int qgd_eval_forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, const double *forcing,
                             double *uv_history, double *out3)
 {
@@ -542,50 +546,118 @@ int qgd_eval_forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, co
     NEED_GRID(h);
     qgdk_ctx &k = h->k;
     if (h->part_world != 1) return fail(h, QGD_ERR_STATE, "partitioned handle: the forced forward sweep is single-GPU");
-    if (h->chunks_eff > 1) return chunked_forward_forced(h, pcof, n_pcof, forcing, uv_history, out3);
-    int rc = forward_begin(h, pcof, n_pcof);
-    if (rc) return rc;
-    if ((rc = forcing_buffers(h, (size_t)k.nt, (size_t)k.scan_blocks))) return rc;
-    if ((rc = upload_forcing(h, forcing, (size_t)k.nt, 0))) return rc;
-    { PhaseTimer t(h, "forcing_terms"); K_TRY(h, qgdk_forcing_terms(&k)); }
-    { PhaseTimer t(h, "sweep_forced"); K_TRY(h, qgdk_forcing_sweep(&k)); }
-    // (the stand-alone guard kernel stores ONE partial penalty per time point; forward_begin sized the fixed-order sum for
-    //  the history pass that fuses the guard work -- fewer, per-block partials -- which this sweep does not run: round 3's
-    //  sum added only the first of them and returned a guard penalty that was too small)
-    k.gpart_n = k.nt;
-    { PhaseTimer t(h, "guard"); K_TRY(h, qgdk_guard_kernel(&k)); }
-    { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target)); }
-    if (uv_history) {
-        { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
-        K_TRY(h, qgdk_forcing_add_derivs(&k));     // w_j = D_j w_0 + E_j
+    const int W = h->chunks_eff;
+    const size_t hstep = (size_t)k.Np * 2 * k.cp;
+    if (W > 1) {
+        if (!pcof && !h->have_tables && k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
+        sweep_void(h); h->resident_window = -1;       // (the window-boundary states are those of the FORCED sweep from here on)
     }
-    if (uv_history && (rc = copy_history_out(h, uv_history, h->save_every))) return rc;
+    size_t nt0 = 0, B0 = 0;
+    int rc;
+    for (int r = 0; r < W; r++) {
+        if (W > 1 && (rc = enter_window(h, pcof, r, true))) return rc;
+        if (r == 0) { nt0 = (size_t)k.nt; B0 = (size_t)k.scan_blocks; }      // (the first window is the longest)
+        k.keep_scal = (r > 0) ? 1 : 0;      // (a later window adds to the guard sum of the ones before it)
+        rc = forward_begin(h, pcof, n_pcof);
+        k.keep_scal = 0;
+        if (rc) return rc;
+        if ((rc = forcing_buffers(h, std::max(nt0, (size_t)k.nt), std::max(B0, (size_t)k.scan_blocks)))) return rc;
+        if ((rc = upload_forcing(h, forcing, (size_t)k.nt, (size_t)k.n_off))) return rc;
+        { PhaseTimer t(h, "forcing_terms"); K_TRY(h, qgdk_forcing_terms(&k)); }
+        { PhaseTimer t(h, "sweep_forced"); K_TRY(h, qgdk_forcing_sweep(&k)); }
+        // (the stand-alone guard kernel stores ONE partial penalty per time point; forward_begin sized the fixed-order sum for
+        //  the history pass that fuses the guard work -- fewer, per-block partials -- which this sweep does not run: round 3's
+        //  sum added only the first of them and returned a guard penalty that was too small)
+        k.gpart_n = k.nt;
+        { PhaseTimer t(h, "guard"); K_TRY(h, qgdk_guard_kernel(&k)); }
+        h->forcing_zero = k.have_guard == 0;
+        if (k.gpart_on && !k.gpart_terminal && k.have_guard) { PhaseTimer t(h, "guard"); K_TRY(h, qgdk_guard_fold(&k)); }
+        if (W > 1)
+            HIP_TRY(h, hipMemcpyAsync(h->chunk_state + (size_t)(r + 1) * hstep, k.hist + (size_t)(k.nt - 1) * hstep, hstep * sizeof(double),
+                                      hipMemcpyDeviceToDevice, k.stream));
+        if (uv_history) {
+            { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
+            K_TRY(h, qgdk_forcing_add_derivs(&k));     // w_j = D_j w_0 + E_j
+            if ((rc = W > 1 ? window_history_out(h, uv_history, h->save_every) : copy_history_out(h, uv_history, h->save_every))) return rc;
+        }
+    }
+    { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target)); }
     if ((rc = fetch_results(h, nullptr, out3))) { (void)finish_copies(h); return rc; }
     return finish_copies(h);
 }
 
 
-// buffers of the forced gradient for (up to) nt time points and B scan blocks
-static int forced_buffers(qgd_handle h, size_t nt, size_t B)
+// buffers of the forced gradient for (up to) nt time points and B scan blocks.  With `bytes`: nothing is allocated, the bytes
+// a call without it would allocate are added to *bytes (0 when the buffers are there already).
+static int forced_buffers(qgd_handle h, size_t nt, size_t B, size_t *bytes = nullptr)
 {
     qgdk_ctx &k = h->k;
     const size_t hstep = (size_t)k.Np * 2 * k.cp, NB = (size_t)k.n_ops * 2 * k.m;
     const size_t cpS = (size_t)k.n_pcof * k.cp, hstepS = (size_t)k.Np * 2 * cpS;
     const size_t key = (nt * 1000003u + (size_t)k.n_pcof) * 4099u + B;
-    int rc;
     if (h->forced_key != key) {
-        free_pool(h->forced_bufs); h->forced_key = 0;
-        if ((rc = dev_alloc(h, h->forced_bufs, &k.fs_BR, nt * NB * hstep))) return rc;
-        if ((rc = dev_alloc(h, h->forced_bufs, &k.fs_BL, nt * NB * hstep))) return rc;
-        if ((rc = dev_alloc(h, h->forced_bufs, &k.fs_phi, B * hstepS))) return rc;
-        if ((rc = dev_alloc(h, h->forced_bufs, &k.fs_bnd, (B + 1) * hstepS))) return rc;
-        if ((rc = dev_alloc(h, h->forced_bufs, &k.fs_gacc, (size_t)k.n_pcof + 1))) return rc;
-        h->fsc_forced = nullptr;      // (the 2m+2 work panels of k_forced_basis: LDS up to 150 KB, else an HBM slab per workgroup)
-        if (qgdk_forced_lds(k.Np, k.m) > 150 * 1024 &&
-            (rc = dev_alloc(h, h->forced_bufs, &h->fsc_forced, nt * (size_t)(k.cp / 8) * (size_t)(2 * k.m + 2) * k.Np * 16))) return rc;
+        int rc = QGD_OK;
+        auto A = [&](double **p, size_t count) -> bool {
+            if (bytes) { *bytes += count * sizeof(double); return true; }
+            return (rc = dev_alloc(h, h->forced_bufs, p, count)) == QGD_OK;
+        };
+        if (!bytes) { free_pool(h->forced_bufs); h->forced_key = 0; h->fsc_forced = nullptr; }
+        if (!A(&k.fs_BR, nt * NB * hstep) || !A(&k.fs_BL, nt * NB * hstep) || !A(&k.fs_phi, B * hstepS) ||
+            !A(&k.fs_bnd, (B + 1) * hstepS) || !A(&k.fs_gacc, (size_t)k.n_pcof + 1)) return rc;
+        // (the 2m+2 work panels of k_forced_basis: LDS up to 150 KB, else an HBM slab per workgroup)
+        if (qgdk_forced_lds(k.Np, k.m) > 150 * 1024 && !A(&h->fsc_forced, nt * (size_t)(k.cp / 8) * (size_t)(2 * k.m + 2) * k.Np * 16)) return rc;
+        if (bytes) return QGD_OK;
         h->forced_key = key;
     }
-    k.fs_scratch = h->fsc_forced;
+    if (!bytes) k.fs_scratch = h->fsc_forced;
+    return QGD_OK;
+}
+
+
+// The terminal part of the forced gradient from s_N, the sensitivities of the final state to every parameter (sN_dev: panels
+// with parameter p in columns p * cp ..), plus the guard part the forced sweeps accumulated in fs_gacc (grad may be NULL):
+//   :Infidelity  -(2/N_ess^2) (<w_N,R> <s_N,R> + <w_N,T> <s_N,T>), T = [R_im; -R_re] (infidelity.jl:13-17)
+//   :Tracking    d(0.5 |w_N - R|^2) = <s_N, w_N - R>;  :Norm  d(0.5 |w_N|^2) = <s_N, w_N>  (eval_grad_forced.jl:160-163)
+// Also returns what the Hessian's terminal part is made of: the overlaps, and with keep_s s_N itself as [2N x c] per parameter.
+struct ForcedTerminal {
+    double f = 0.0;                 // -2 / N_ess^2
+    std::vector<double> sR, sT;     // <s_N,R>, <s_N,T> of every parameter
+    std::vector<double> s;          // (keep_s) s_N of parameter p at p * 2N * c
+};
+
+static int forced_terminal(qgd_handle h, const double *sN_dev, double *grad, ForcedTerminal &t, bool keep_s = false)
+{
+    qgdk_ctx &k = h->k;
+    const size_t np = (size_t)k.n_pcof, N = k.N, L = 2 * N * k.c, hstep = (size_t)k.Np * 2 * k.cp, PWs = 2 * np * k.cp;
+    std::vector<double> sN((size_t)k.Np * PWs), gacc(np), scal(4), d, s_one(L);
+    HIP_TRY(h, hipMemcpy(sN.data(), sN_dev, sN.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (k.cost_type) {     // :Tracking / :Norm need the final state itself: d = w_N - R, or w_N
+        std::vector<double> wN(hstep);
+        HIP_TRY(h, hipMemcpy(wN.data(), k.hist + ((size_t)k.nt - 1) * hstep, hstep * sizeof(double), hipMemcpyDeviceToHost));
+        d.resize(L);
+        unpack_panel(d.data(), 2 * N, wN.data(), 2 * k.cp, k.N, k.c);
+        if (k.cost_type == QGD_COST_TRACKING) for (size_t e = 0; e < L; e++) d[e] -= h->target_host[e];
+    }
+    HIP_TRY(h, hipMemcpy(gacc.data(), k.fs_gacc, sizeof(double) * np, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(scal.data(), k.scal, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    const double a = scal[0], b = scal[1];
+    t.f = -2.0 / ((double)k.n_ess * k.n_ess);
+    t.sR.assign(np, 0.0); t.sT.assign(np, 0.0); t.s.assign(keep_s ? np * L : 0, 0.0);
+    for (size_t p = 0; p < np; p++) {
+        double *s = keep_s ? t.s.data() + p * L : s_one.data();
+        unpack_panel(s, 2 * N, sN.data() + 2 * p * k.cp, (int)PWs, k.N, k.c);
+        double sR = 0.0, sT = 0.0, sW = 0.0;
+        for (size_t col = 0; col < (size_t)k.c; col++)
+            for (size_t i = 0; i < N; i++) {
+                const size_t e = i + 2 * N * col;
+                const double sre = s[e], sim = s[N + e], rre = h->target_host[e], rim = h->target_host[N + e];
+                sR += sre * rre + sim * rim;
+                sT += sre * rim - sim * rre;
+                if (k.cost_type) sW += sre * d[e] + sim * d[N + e];
+            }
+        t.sR[p] = sR; t.sT[p] = sT;
+        if (grad) grad[p] = (k.cost_type ? sW : t.f * (a * sR + b * sT)) + gacc[p];
+    }
     return QGD_OK;
 }
 
@@ -602,72 +674,36 @@ int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, doubl
     if (h->part_world != 1) return fail(h, QGD_ERR_STATE, "partitioned handle: the forced gradient is single-GPU");
     int rc;
     if ((rc = run_forward(h, pcof, n_pcof))) return rc;      // (a windowed grid: every window, the state at each window start kept)
-    const size_t hstep = (size_t)k.Np * 2 * k.cp;
-    const size_t cpS = (size_t)k.n_pcof * k.cp, hstepS = (size_t)k.Np * 2 * cpS;
-    size_t nt = k.nt, B = k.scan_blocks;
-    if (h->chunks_eff == 1) {
-        if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
-        if ((rc = forced_buffers(h, nt, B))) return rc;
-        HIP_TRY(h, hipMemsetAsync(k.fs_bnd, 0, hstepS * sizeof(double), k.stream));
-        HIP_TRY(h, hipMemsetAsync(k.fs_gacc, 0, ((size_t)k.n_pcof + 1) * sizeof(double), k.stream));
+    const int W = h->chunks_eff;
+    const size_t hstepS = (size_t)k.Np * 2 * k.n_pcof * k.cp;
+    // A windowed grid: windows in order, each forms its matrices and forward history again from its stored start state (as the
+    // adjoint pass does), the sensitivities of all parameters continue from where the previous window left them, the guard part
+    // of the gradient accumulates.  (eval_grad_forced.jl:17-194 keeps no matrices either: one forced sweep per parameter.)
+    // The sweep record differs between the grids: a resident one keeps run_forward's sweep (SWEEP_GENERAL, with its stage
+    // derivatives), a windowed one ends at SWEEP_NONE because chunk_forward's reruns go through sweep_begin.
+    for (int r = 0; r < W; r++) {
+        if (W > 1 && (rc = chunk_forward(h, pcof, n_pcof, r, true))) return rc;
+        if (r == 0) {      // (the first window is the longest)
+            if ((rc = forced_buffers(h, (size_t)k.nt, (size_t)k.scan_blocks))) return rc;
+            HIP_TRY(h, hipMemsetAsync(k.fs_bnd, 0, hstepS * sizeof(double), k.stream));
+            HIP_TRY(h, hipMemsetAsync(k.fs_gacc, 0, ((size_t)k.n_pcof + 1) * sizeof(double), k.stream));
+        }
+        if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = W == 1; }
         { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); }
         { PhaseTimer t(h, "forced_sweeps"); K_TRY(h, qgdk_forced_chains(&k)); }
-    } else {
-        // Windows in order: each forms its matrices and forward history again from its stored start state (as the adjoint pass
-        // does), the sensitivities of all parameters continue from where the previous window left them, the guard part of the
-        // gradient accumulates.  (eval_grad_forced.jl:17-194 keeps no matrices either: one forced sweep per parameter.)
-        size_t nt0 = 0, B0 = 0;
-        for (int r = 0; r < h->chunks_eff; r++) {
-            if ((rc = chunk_forward(h, pcof, n_pcof, r, true))) return rc;
-            if (r == 0) {
-                nt0 = (size_t)k.nt; B0 = (size_t)k.scan_blocks;      // (the first window is the longest)
-                if ((rc = forced_buffers(h, nt0, B0))) return rc;
-                HIP_TRY(h, hipMemsetAsync(k.fs_bnd, 0, hstepS * sizeof(double), k.stream));
-                HIP_TRY(h, hipMemsetAsync(k.fs_gacc, 0, ((size_t)k.n_pcof + 1) * sizeof(double), k.stream));
-            }
-            k.fs_scratch = h->fsc_forced;
-            { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
-            { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); }
-            { PhaseTimer t(h, "forced_sweeps"); K_TRY(h, qgdk_forced_chains(&k)); }
-            nt = k.nt; B = k.scan_blocks;
-            if (r + 1 < h->chunks_eff)      // s at the start of the next window
-                HIP_TRY(h, hipMemcpyAsync(k.fs_bnd, k.fs_bnd + B * hstepS, hstepS * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
-        }
+        if (r + 1 < W)      // s at the start of the next window
+            HIP_TRY(h, hipMemcpyAsync(k.fs_bnd, k.fs_bnd + (size_t)k.scan_blocks * hstepS, hstepS * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
     }
     if ((rc = check_status(h))) return rc;
-    std::vector<double> sN(hstepS), gacc(k.n_pcof), scal(4), wN;
-    HIP_TRY(h, hipMemcpy(sN.data(), k.fs_bnd + B * hstepS, hstepS * sizeof(double), hipMemcpyDeviceToHost));
-    if (k.cost_type) {     // :Tracking / :Norm need the final state itself (eval_grad_forced.jl:160-163)
-        wN.resize(hstep);
-        HIP_TRY(h, hipMemcpy(wN.data(), k.hist + (nt - 1) * hstep, hstep * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(h, hipMemcpy(gacc.data(), k.fs_gacc, sizeof(double) * k.n_pcof, hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(scal.data(), k.scal, 3 * sizeof(double), hipMemcpyDeviceToHost));
-    // d(infidelity) = -(2/N_ess^2) (<w_N,R> <s_N,R> + <w_N,T> <s_N,T>), T = [R_im; -R_re] (infidelity.jl:13-17)
-    const size_t N = k.N, PWs = 2 * cpS;
-    const double a = scal[0], b = scal[1], f = -2.0 / ((double)k.n_ess * k.n_ess);
-    for (int p = 0; p < k.n_pcof; p++) {
-        double sR = 0.0, sT = 0.0, sW = 0.0;
-        for (int col = 0; col < k.c; col++)
-            for (size_t i = 0; i < N; i++) {
-                const size_t o = panel_index((int)i, p * k.cp + col, (int)PWs);
-                const double sre = sN[o], sim = sN[o + 8];
-                const double rre = h->target_host[i + 2 * N * col], rim = h->target_host[N + i + 2 * N * col];
-                sR += sre * rre + sim * rim;
-                sT += sre * rim - sim * rre;
-                if (k.cost_type) {      // d(0.5 |w_N - R|^2) = <s_N, w_N - R>,  d(0.5 |w_N|^2) = <s_N, w_N>
-                    const size_t ow = panel_index((int)i, col, 2 * k.cp);
-                    const double dre = wN[ow] - (k.cost_type == QGD_COST_TRACKING ? rre : 0.0);
-                    const double dim = wN[ow + 8] - (k.cost_type == QGD_COST_TRACKING ? rim : 0.0);
-                    sW += sre * dre + sim * dim;
-                }
-            }
-        grad[p] = (k.cost_type ? sW : f * (a * sR + b * sT)) + gacc[p];
-    }
-    return QGD_OK;
+    ForcedTerminal t;
+    return forced_terminal(h, k.fs_bnd + (size_t)k.scan_blocks * hstepS, grad, t);
 }
 
 
+// eval_adjoint (forward_evolution.jl:352-483): lambda from the given terminal condition lambda_N and forcing, no forward
+// history (none is read).  A windowed grid runs its windows in reverse; each forms its matrices, takes its slice of the forcing
+// and the y the next window ended in (the last one: y_N = L_N^H lambda_N), and writes its share of lambda_history (global time
+// indices n_off+1 .. n_off+nt-1).
 int qgd_eval_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, const double *terminal_condition,
                      const double *forcing, double *lambda_history)
 {
@@ -677,53 +713,51 @@ int qgd_eval_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, const dou
     NEED_GRID(h);
     qgdk_ctx &k = h->k;
     if (h->part_world != 1) return fail(h, QGD_ERR_STATE, "partitioned handle: eval_adjoint is single-GPU");
-    if (h->chunks_eff > 1) return chunked_eval_adjoint(h, pcof, n_pcof, terminal_condition, forcing, lambda_history);
-    int rc = forward_begin(h, pcof, n_pcof);          // tables, L/R, inverses, propagators, block propagators
-    if (rc) return rc;
-    // the second scan level (super-block propagators) is produced by the forward boundary phase
-    { PhaseTimer t(h, "sweep_forward2"); K_TRY(h, qgdk_forward_finish(&k)); }
-    const size_t Np = k.Np, PWc = 2 * k.cp, hstep = Np * PWc, nt = k.nt, N = k.N, n2 = 2 * N, m = k.m;
-    // forcing [2N, nt, c] and terminal condition [2N, c] into panel layout
-    std::vector<double> f(nt * hstep, 0.0), lamN(hstep, 0.0);
-    for (size_t col = 0; col < (size_t)k.c; col++) {
-        for (size_t i = 0; i < N; i++) {
-            size_t o = panel_index((int)i, (int)col, (int)PWc);
-            lamN[o] = terminal_condition[i + n2 * col];
-            lamN[o + 8] = terminal_condition[N + i + n2 * col];
-        }
+    const int W = h->chunks_eff;
+    const size_t PWc = 2 * k.cp, hstep = (size_t)k.Np * PWc, n2 = 2 * (size_t)k.N, m = k.m, ntg = k.nt_glob;
+    if (W > 1) {
+        if (!pcof && !h->have_tables && k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
+        memset(lambda_history, 0, sizeof(double) * n2 * (m + 1) * ntg * k.c);      // (a window writes only its j = 0 columns)
+        sweep_void(h); h->resident_window = -1;      // (the buffers will hold no window's forward history)
+    }
+    // terminal condition [2N, c] and forcing [2N, nt_glob, c] into panel layout
+    std::vector<double> lamN(hstep, 0.0), f;
+    pack_panel(lamN.data(), (int)PWc, terminal_condition, k.N, k.c, n2);
+    int rc;
+    for (int r = W - 1; r >= 0; r--) {
+        if (W > 1 && (rc = enter_window(h, pcof, r, false))) return rc;
+        const size_t nt = k.nt;
+        if ((rc = forward_begin(h, pcof, n_pcof))) return rc;      // tables, L/R, inverses, propagators, block propagators
+        { PhaseTimer t(h, "sweep_forward2"); K_TRY(h, qgdk_forward_finish(&k)); }      // (the super-block propagators)
+        f.assign(nt * hstep, 0.0);
         if (forcing)
-            for (size_t n = 0; n < nt; n++) for (size_t i = 0; i < N; i++) {
-                size_t o = n * hstep + panel_index((int)i, (int)col, (int)PWc);
-                const double *src = forcing + (col * nt + n) * n2;
-                f[o] = src[i]; f[o + 8] = src[N + i];
-            }
-    }
-    HIP_TRY(h, hipMemcpyAsync(k.forcing, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, k.stream));
-    h->forcing_zero = false;
-    HIP_TRY(h, hipMemcpyAsync(k.lam + (nt - 1) * hstep, lamN.data(), hstep * sizeof(double), hipMemcpyHostToDevice, k.stream));
-    // y_N = L(t_N)^H lambda_N  (the terminal condition is lambda itself here, forward_evolution.jl:411-414)
-    K_TRY(h, qgdk_apply_LH(&k));
-    if ((rc = adjoint_begin(h))) return rc;
-    { PhaseTimer t(h, "sweep_adjoint2"); K_TRY(h, qgdk_adjoint_finish(&k)); }
-    { PhaseTimer t(h, "lambda"); K_TRY(h, qgdk_lambda(&k)); }
-    if ((rc = check_status(h))) return rc;
-    if (h->lambda_derivs) {      // the reference's derivative columns too (forward_evolution.jl:427-433, :471-480)
-        HIP_TRY(h, hipMemcpyAsync(k.lam + (nt - 1) * hstep, lamN.data(), hstep * sizeof(double), hipMemcpyHostToDevice, k.stream));
-        rc = copy_lambda_full_out(h, lambda_history);
-        const int rc2 = finish_copies(h);
-        return rc ? rc : rc2;
-    }
-    std::vector<double> l(nt * hstep);
-    HIP_TRY(h, hipMemcpy(l.data(), k.lam, l.size() * sizeof(double), hipMemcpyDeviceToHost));
-    memset(lambda_history, 0, sizeof(double) * n2 * (m + 1) * nt * k.c);
-    for (size_t col = 0; col < (size_t)k.c; col++) for (size_t n = 1; n < nt; n++) {
-        double *dst = lambda_history + ((col * nt + n) * (m + 1)) * n2;
-        const double *src = (n == nt - 1) ? lamN.data() : l.data() + n * hstep;   // lambda_N is the given one
-        for (size_t i = 0; i < N; i++) {
-            size_t o = panel_index((int)i, (int)col, (int)PWc);
-            dst[i] = src[o]; dst[N + i] = src[o + 8];
+            for (size_t n = 0; n < nt; n++) pack_panel(f.data() + n * hstep, (int)PWc, forcing + ((size_t)k.n_off + n) * n2, k.N, k.c, ntg * n2);
+        // (on the library's stream: behind the history pass, which writes the guard forcing of the window into this buffer)
+        HIP_TRY(h, hipMemcpyAsync(k.forcing, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, k.stream));
+        HIP_TRY(h, hipStreamSynchronize(k.stream));         // (f is filled again for the next window)
+        h->forcing_zero = false;
+        if (r == W - 1) {      // y_N = L(t_N)^H lambda_N  (the terminal condition is lambda itself here, forward_evolution.jl:411-414)
+            HIP_TRY(h, hipMemcpyAsync(k.lam + (nt - 1) * hstep, lamN.data(), hstep * sizeof(double), hipMemcpyHostToDevice, k.stream));
+            K_TRY(h, qgdk_apply_LH(&k));
+        } else {               // y at the end of this window = y at the start of the next one
+            for (double *dst : {k.yhist + (nt - 1) * hstep, k.bndY + (size_t)k.scan_blocks * hstep, k.bndY2 + (size_t)k.scan_blocks2 * hstep})
+                HIP_TRY(h, hipMemcpyAsync(dst, h->carry_y, hstep * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
         }
+        if ((rc = adjoint_begin(h))) return rc;
+        { PhaseTimer t(h, "sweep_adjoint2"); K_TRY(h, qgdk_adjoint_finish(&k)); }
+        { PhaseTimer t(h, "lambda"); K_TRY(h, qgdk_lambda(&k)); }
+        if ((rc = check_status(h))) return rc;
+        if (r == W - 1)      // lambda_N is the given one (not L_N^-H L_N^H of it)
+            HIP_TRY(h, hipMemcpyAsync(k.lam + (nt - 1) * hstep, lamN.data(), hstep * sizeof(double), hipMemcpyHostToDevice, k.stream));
+        // (with qgd_set_lambda_derivatives the reference's derivative columns too, forward_evolution.jl:427-433, :471-480)
+        // (a resident grid takes copy_panels_out, which zero-fills the staging buffer it allocates: time index 0 stays zero)
+        if (W > 1) rc = h->lambda_derivs ? window_lambda_full_out(h, lambda_history) : window_panels_out(h, k.lam, &h->stage_lam, lambda_history, m + 1, 1);
+        else rc = h->lambda_derivs ? copy_lambda_full_out(h, lambda_history) : copy_panels_out(h, k.lam, &h->stage_lam, lambda_history, m + 1, 1);
+        const int rc2 = finish_copies(h);      // (copy_*_out leave their download running)
+        if (rc || rc2) return rc ? rc : rc2;
+        if (r > 0) HIP_TRY(h, hipMemcpyAsync(h->carry_y, k.yhist, hstep * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
     }
+    HIP_TRY(h, hipStreamSynchronize(k.stream));
     return QGD_OK;
 }
 
@@ -741,10 +775,7 @@ int qgd_apply_hamiltonian(qgd_handle h, int32_t time_index, int32_t deriv_order,
         return fail(h, QGD_ERR_ARGUMENT, "time index or derivative order out of range");
     const size_t PWc = 2 * k.cp, cnt = (size_t)k.Np * PWc;
     std::vector<double> p(cnt, 0.0), q(cnt, 0.0);
-    for (int col = 0; col < k.c; col++) for (int i = 0; i < k.N; i++) {
-        size_t o = panel_index(i, col, (int)PWc);
-        p[o] = in[i + (size_t)2 * k.N * col]; p[o + 8] = in[k.N + i + (size_t)2 * k.N * col];
-    }
+    pack_panel(p.data(), (int)PWc, in, k.N, k.c, (size_t)2 * k.N);
     double *din = nullptr, *dout = nullptr;
     HIP_TRY(h, hipMalloc((void **)&din, cnt * sizeof(double)));
     HIP_TRY(h, hipMalloc((void **)&dout, cnt * sizeof(double)));
@@ -754,10 +785,7 @@ int qgd_apply_hamiltonian(qgd_handle h, int32_t time_index, int32_t deriv_order,
     if (!kr && e == hipSuccess) e = hipMemcpy(q.data(), dout, cnt * sizeof(double), hipMemcpyDeviceToHost);
     (void)hipFree(din); (void)hipFree(dout);
     if (kr || e != hipSuccess) return fail(h, QGD_ERR_NO_DEVICE, "apply kernel failed");
-    for (int col = 0; col < k.c; col++) for (int i = 0; i < k.N; i++) {
-        size_t o = panel_index(i, col, (int)PWc);
-        out[i + (size_t)2 * k.N * col] = q[o]; out[k.N + i + (size_t)2 * k.N * col] = q[o + 8];
-    }
+    unpack_panel(out, (size_t)2 * k.N, q.data(), (int)PWc, k.N, k.c);
     return QGD_OK;
 }
 
@@ -978,9 +1006,7 @@ int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *h
         free_pool(h->hess_bufs); h->hess_key = 0;
         // everything this call allocates: its own buffers and, when they are not there yet, the forced gradient's (forced_buffers)
         size_t bytes = (n_shist + n_ws + n_Z + n_half + n_slab + n_zt + n_Y) * sizeof(double);
-        const size_t fkey = (nt * 1000003u + np) * 4099u + (size_t)k.scan_blocks;
-        if (h->forced_key != fkey)
-            bytes += (2 * nt * NB * hstep + (2 * (size_t)k.scan_blocks + 1) * hstepS + np + 1) * sizeof(double);
+        (void)forced_buffers(h, nt, k.scan_blocks, &bytes);
         size_t fr = 0, tot = 0;
         if ((h->mem_budget && bytes > h->mem_budget) || (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr))
             return fail(h, QGD_ERR_MEMORY, "the sensitivity history of qgd_eval_hessian does not fit (" + std::to_string(bytes) + " bytes needed)");
@@ -1013,50 +1039,21 @@ int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *h
     { PhaseTimer t(h, "hess_terms"); K_TRY(h, qgdk_hess_kernels(&k, shist, Z, half, slab, zt, Y)); }
     if (k.have_guard) { PhaseTimer t(h, "hess_guard"); K_TRY(h, qgdk_hess_gram(&k, shist, ws, gpartial, Gm)); }
     if ((rc = check_status(h))) return rc;
-    std::vector<double> sN(hstepS), gacc(np), scal(4), wN, Yh(np * np), Gh(np * np);
-    HIP_TRY(h, hipMemcpy(sN.data(), shist + (nt - 1) * hstepS, hstepS * sizeof(double), hipMemcpyDeviceToHost));
-    if (k.cost_type) {
-        wN.resize(hstep);
-        HIP_TRY(h, hipMemcpy(wN.data(), k.hist + (nt - 1) * hstep, hstep * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(h, hipMemcpy(gacc.data(), k.fs_gacc, sizeof(double) * np, hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(scal.data(), k.scal, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    // terminal part: the overlaps <s_N,R>, <s_N,T> of every parameter (:Infidelity) or s_N itself (:Tracking / :Norm)
+    ForcedTerminal t;
+    if ((rc = forced_terminal(h, shist + (nt - 1) * hstepS, grad, t, k.cost_type != 0))) return rc;
+    std::vector<double> Yh(np * np), Gh(np * np);
     HIP_TRY(h, hipMemcpy(Yh.data(), Y, np * np * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(h, hipMemcpy(Gh.data(), Gm, np * np * sizeof(double), hipMemcpyDeviceToHost));
-    // terminal part: the overlaps <s_N,R>, <s_N,T> of every parameter (:Infidelity) or s_N itself (:Tracking / :Norm)
-    const size_t N = k.N, PWs = 2 * cpS;
-    const double a = scal[0], b = scal[1], f = -2.0 / ((double)k.n_ess * k.n_ess);
-    std::vector<double> sR(np), sT(np), sv(k.cost_type ? np * 2 * N * k.c : 0);
-    for (size_t p = 0; p < np; p++) {
-        double r = 0.0, t = 0.0, sW = 0.0;
-        for (int col = 0; col < k.c; col++)
-            for (size_t i = 0; i < N; i++) {
-                const size_t o = panel_index((int)i, (int)p * k.cp + col, (int)PWs);
-                const double sre = sN[o], sim = sN[o + 8];
-                const double rre = h->target_host[i + 2 * N * col], rim = h->target_host[N + i + 2 * N * col];
-                r += sre * rre + sim * rim;
-                t += sre * rim - sim * rre;
-                if (k.cost_type) {
-                    const size_t ow = panel_index((int)i, col, 2 * k.cp);
-                    const double dre = wN[ow] - (k.cost_type == QGD_COST_TRACKING ? rre : 0.0);
-                    const double dim = wN[ow + 8] - (k.cost_type == QGD_COST_TRACKING ? rim : 0.0);
-                    sW += sre * dre + sim * dim;
-                    sv[(p * k.c + col) * 2 * N + i] = sre;
-                    sv[(p * k.c + col) * 2 * N + N + i] = sim;
-                }
-            }
-        sR[p] = r; sT[p] = t;
-        if (grad) grad[p] = (k.cost_type ? sW : f * (a * r + b * t)) + gacc[p];
-    }
-    const size_t L = 2 * N * k.c;
+    const size_t L = 2 * (size_t)k.N * k.c;
     for (size_t p = 0; p < np; p++)
         for (size_t q = 0; q < np; q++) {
             double phi;
             if (k.cost_type) {
                 phi = 0.0;
-                for (size_t e = 0; e < L; e++) phi += sv[p * L + e] * sv[q * L + e];
+                for (size_t e = 0; e < L; e++) phi += t.s[p * L + e] * t.s[q * L + e];
             } else {
-                phi = f * (sR[p] * sR[q] + sT[p] * sT[q]);
+                phi = t.f * (t.sR[p] * t.sR[q] + t.sT[p] * t.sT[q]);
             }
             hess[p * np + q] = (Yh[p * np + q] + Yh[q * np + p]) + Gh[p * np + q] + phi;      // (Gh: both triangles from the same sums)
         }

@@ -1,4 +1,4 @@
-// qgd_host_windows.cpp -- host side of the C ABI (include/qgd.h), time grids in bounded memory (qgd_set_memory_budget): the windowed forward, adjoint and forced sweeps.
+// qgd_host_windows.cpp -- host side of the C ABI (include/qgd.h), time grids in bounded memory (qgd_set_memory_budget): window entry, the windowed forward and adjoint passes and their outputs, the forced sweep's buffers.
 #include "qgd_host.h"
 
 namespace qgdh {
@@ -100,7 +100,7 @@ int window_panels_out(qgd_handle h, const double *panels, double **stage, double
 
 // qgd_set_control_tables on a windowed grid: the window's slice of the caller's tables goes to the device before the
 // window's matrices are built (with pcof the tables kernel forms them from the basis, which covers the whole grid)
-int window_tables(qgd_handle h)
+static int window_tables(qgd_handle h)
 {
     qgdk_ctx &k = h->k;
     const size_t per = (size_t)(k.m + 1) * k.n_ops, cnt = (size_t)k.nt * per, off = (size_t)k.n_off * per;
@@ -117,16 +117,30 @@ int window_tables(qgd_handle h)
 }
 
 
-int chunk_forward(qgd_handle h, const double *pcof, int n_pcof, int r, bool rerun)
+// window r takes over the per-time-point buffers: its layout, its slice of the caller's control tables (no pcof) and, with
+// with_start_state, the state the forward sweep of the window starts from (stored by the window before it)
+int enter_window(qgd_handle h, const double *pcof, int r, bool with_start_state)
 {
     qgdk_ctx &k = h->k;
     int rc = plan_windows(h, h->chunks_req, r);
     if (rc) return rc;
     if (!pcof && k.n_ops > 0 && (rc = window_tables(h))) return rc;
+    if (with_start_state) {
+        const size_t hstep = (size_t)k.Np * 2 * k.cp;
+        const double *start = h->chunk_state + (size_t)r * hstep;
+        for (double *dst : {k.psi0, k.hist, k.bnd, k.bnd2})
+            HIP_TRY(h, hipMemcpyAsync(dst, start, hstep * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
+    }
+    return QGD_OK;
+}
+
+
+int chunk_forward(qgd_handle h, const double *pcof, int n_pcof, int r, bool rerun)
+{
+    qgdk_ctx &k = h->k;
+    int rc = enter_window(h, pcof, r, true);
+    if (rc) return rc;
     const size_t hstep = (size_t)k.Np * 2 * k.cp;
-    const double *start = h->chunk_state + (size_t)r * hstep;
-    for (double *dst : {k.psi0, k.hist, k.bnd, k.bnd2})
-        HIP_TRY(h, hipMemcpyAsync(dst, start, hstep * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
     k.keep_scal = (r > 0 || rerun) ? 1 : 0;
     double *scal_real = k.scal;
     if (rerun) k.scal = h->scal_scratch;          // (the guard sum of this window was counted by the forward pass)
@@ -199,69 +213,6 @@ int chunked_adjoint(qgd_handle h, double *lambda_history, double *adjoint_forcin
 }
 
 
-// eval_adjoint on a windowed grid: windows in reverse; each forms its matrices, takes its slice of the caller's forcing and
-// the y the next window ended in (the last one: y_N = L_N^H lambda_N from the given terminal condition), runs the adjoint
-// scan and lambda, and writes its share of lambda_history (global time indices n_off+1 .. n_off+nt-1).  No forward history is
-// needed (forward_evolution.jl:352-483 reads none).
-int chunked_eval_adjoint(qgd_handle h, const double *pcof, int n_pcof, const double *terminal_condition, const double *forcing,
-                         double *lambda_history)
-{
-    qgdk_ctx &k = h->k;
-    if (!pcof && !h->have_tables && k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
-    const size_t Np = k.Np, PWc = 2 * k.cp, hstep = Np * PWc, N = k.N, n2 = 2 * N, m = k.m, ntg = (size_t)h->nsteps + 1;
-    const int W = h->chunks_eff;
-    std::vector<double> lamN(hstep, 0.0), f;
-    for (size_t col = 0; col < (size_t)k.c; col++)
-        for (size_t i = 0; i < N; i++) {
-            const size_t o = panel_index((int)i, (int)col, (int)PWc);
-            lamN[o] = terminal_condition[i + n2 * col];
-            lamN[o + 8] = terminal_condition[N + i + n2 * col];
-        }
-    memset(lambda_history, 0, sizeof(double) * n2 * (m + 1) * ntg * k.c);
-    sweep_void(h); h->resident_window = -1;      // (the buffers will hold no window's forward history)
-    int rc;
-    for (int r = W - 1; r >= 0; r--) {
-        if ((rc = plan_windows(h, h->chunks_req, r))) return rc;
-        const size_t nt = k.nt, n_off = k.n_off;
-        if (!pcof && k.n_ops > 0 && (rc = window_tables(h))) return rc;
-        if ((rc = forward_begin(h, pcof, n_pcof))) return rc;
-        { PhaseTimer t(h, "sweep_forward2"); K_TRY(h, qgdk_forward_finish(&k)); }      // (the super-block propagators)
-        f.assign(nt * hstep, 0.0);
-        if (forcing)
-            for (size_t col = 0; col < (size_t)k.c; col++)
-                for (size_t n = 0; n < nt; n++) {
-                    const double *src = forcing + (col * ntg + n_off + n) * n2;
-                    for (size_t i = 0; i < N; i++) {
-                        const size_t o = n * hstep + panel_index((int)i, (int)col, (int)PWc);
-                        f[o] = src[i]; f[o + 8] = src[N + i];
-                    }
-                }
-        // (on the library's stream: behind the history pass, which writes the guard forcing of the window into this buffer)
-        HIP_TRY(h, hipMemcpyAsync(k.forcing, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, k.stream));
-        HIP_TRY(h, hipStreamSynchronize(k.stream));         // (f is filled again for the next window)
-        h->forcing_zero = false;
-        if (r == W - 1) {
-            HIP_TRY(h, hipMemcpyAsync(k.lam + (nt - 1) * hstep, lamN.data(), hstep * sizeof(double), hipMemcpyHostToDevice, k.stream));
-            K_TRY(h, qgdk_apply_LH(&k));
-        } else {
-            for (double *dst : {k.yhist + (nt - 1) * hstep, k.bndY + (size_t)k.scan_blocks * hstep, k.bndY2 + (size_t)k.scan_blocks2 * hstep})
-                HIP_TRY(h, hipMemcpyAsync(dst, h->carry_y, hstep * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
-        }
-        if ((rc = adjoint_begin(h))) return rc;
-        { PhaseTimer t(h, "sweep_adjoint2"); K_TRY(h, qgdk_adjoint_finish(&k)); }
-        { PhaseTimer t(h, "lambda"); K_TRY(h, qgdk_lambda(&k)); }
-        if ((rc = check_status(h))) return rc;
-        if (r == W - 1)      // lambda_N is the given one (not L_N^-H L_N^H of it)
-            HIP_TRY(h, hipMemcpyAsync(k.lam + (nt - 1) * hstep, lamN.data(), hstep * sizeof(double), hipMemcpyHostToDevice, k.stream));
-        if ((rc = h->lambda_derivs ? window_lambda_full_out(h, lambda_history)
-                                   : window_panels_out(h, k.lam, &h->stage_lam, lambda_history, m + 1, 1))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->carry_y, k.yhist, hstep * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
-    }
-    HIP_TRY(h, hipStreamSynchronize(k.stream));
-    return QGD_OK;
-}
-
-
 // buffers of the forced forward sweep for (up to) nt time points and B scan blocks
 int forcing_buffers(qgd_handle h, size_t nt, size_t B)
 {
@@ -292,67 +243,13 @@ int forcing_buffers(qgd_handle h, size_t nt, size_t B)
 int upload_forcing(qgd_handle h, const double *forcing, size_t nt, size_t n_off)
 {
     qgdk_ctx &k = h->k;
-    const size_t m = k.m, N = k.N, n2 = 2 * N, PWc = 2 * k.cp, hstep = (size_t)k.Np * PWc, ntg = (size_t)h->nsteps + 1;
+    const size_t m = k.m, n2 = 2 * (size_t)k.N, PWc = 2 * k.cp, hstep = (size_t)k.Np * PWc, ntg = (size_t)h->nsteps + 1;
     std::vector<double> f(nt * m * hstep, 0.0);
-    for (size_t col = 0; col < (size_t)k.c; col++) for (size_t n = 0; n < nt; n++) for (size_t j = 0; j < m; j++) {
-        const double *src = forcing + ((col * ntg + n_off + n) * m + j) * n2;
-        double *dst = f.data() + (n * m + j) * hstep;
-        for (size_t i = 0; i < N; i++) {
-            const size_t o = panel_index((int)i, (int)col, (int)PWc);
-            dst[o] = src[i]; dst[o + 8] = src[N + i];
-        }
-    }
+    for (size_t n = 0; n < nt; n++) for (size_t j = 0; j < m; j++)
+        pack_panel(f.data() + (n * m + j) * hstep, (int)PWc, forcing + ((n_off + n) * m + j) * n2, k.N, k.c, ntg * m * n2);
     HIP_TRY(h, hipMemcpyAsync(k.ff_F, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, k.stream));
     HIP_TRY(h, hipStreamSynchronize(k.stream));
     return QGD_OK;
-}
-
-
-
-// eval_forward(...; forcing) on a windowed grid (forward_evolution.jl:118-129,167-206): windows in order, each from the
-// forced state the previous one ended in, with its slice of the caller's forcing; the guard penalty accumulates over the
-// windows, the overlaps come from the final state; uv_history (stage derivatives w_j = D_j w_0 + E_j included) window by
-// window as in chunked_forward.
-int chunked_forward_forced(qgd_handle h, const double *pcof, int n_pcof, const double *forcing, double *uv_history, double *out3)
-{
-    qgdk_ctx &k = h->k;
-    if (!pcof && !h->have_tables && k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
-    const size_t hstep = (size_t)k.Np * 2 * k.cp;
-    int rc;
-    sweep_void(h); h->resident_window = -1;       // (the window-boundary states are those of the FORCED sweep from here on)
-    size_t nt0 = 0, B0 = 0;
-    for (int r = 0; r < h->chunks_eff; r++) {
-        if ((rc = plan_windows(h, h->chunks_req, r))) return rc;
-        if (r == 0) { nt0 = (size_t)k.nt; B0 = (size_t)k.scan_blocks; }      // (the first window is the longest)
-        if (!pcof && k.n_ops > 0 && (rc = window_tables(h))) return rc;
-        const double *start = h->chunk_state + (size_t)r * hstep;
-        for (double *dst : {k.psi0, k.hist, k.bnd, k.bnd2})
-            HIP_TRY(h, hipMemcpyAsync(dst, start, hstep * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
-        k.keep_scal = (r > 0) ? 1 : 0;
-        rc = forward_begin(h, pcof, n_pcof);
-        if (!rc) rc = forcing_buffers(h, std::max(nt0, (size_t)k.nt), std::max(B0, (size_t)k.scan_blocks));
-        if (!rc) rc = upload_forcing(h, forcing, (size_t)k.nt, (size_t)k.n_off);
-        if (!rc && qgdk_forcing_terms(&k)) rc = fail(h, QGD_ERR_NO_DEVICE, "forcing terms failed to launch");
-        if (!rc && qgdk_forcing_sweep(&k)) rc = fail(h, QGD_ERR_NO_DEVICE, "forced sweep failed to launch");
-        if (!rc) {
-            k.gpart_n = k.nt;                                 // (one partial penalty per time point: the stand-alone guard kernel)
-            if (qgdk_guard_kernel(&k)) rc = fail(h, QGD_ERR_NO_DEVICE, "guard kernel failed to launch");
-            if (k.have_guard == 0) h->forcing_zero = true; else h->forcing_zero = false;
-        }
-        if (!rc && k.gpart_on && k.have_guard && qgdk_guard_fold(&k)) rc = fail(h, QGD_ERR_NO_DEVICE, "guard fold failed to launch");
-        k.keep_scal = 0;
-        if (rc) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->chunk_state + (size_t)(r + 1) * hstep, k.hist + (size_t)(k.nt - 1) * hstep, hstep * sizeof(double),
-                                  hipMemcpyDeviceToDevice, k.stream));
-        if (uv_history) {
-            { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
-            K_TRY(h, qgdk_forcing_add_derivs(&k));            // w_j = D_j w_0 + E_j
-            if ((rc = window_history_out(h, uv_history, h->save_every))) return rc;
-        }
-    }
-    { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target)); }
-    if ((rc = fetch_results(h, nullptr, out3, nullptr))) { (void)finish_copies(h); return rc; }
-    return finish_copies(h);
 }
 
 }  // namespace qgdh
