@@ -375,6 +375,17 @@ int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, doubl
  * next call) do not fit the memory budget or the free device memory.  DESIGN.md section 4c. */
 int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *hess, double *grad);
 
+/* Exact Hessian-vector products hv = H v of the same Hessian by a second-order adjoint sweep, without forming H or the
+ * sensitivity history of the parameters: one forced sweep with the single direction v, one adjoint sweep with a forcing, one
+ * gradient contraction per vector.  v and hv are [n_pcof x n_vec] column-major; grad may be NULL, else it receives the
+ * adjoint gradient at pcof.  What does not depend on v (forward sweep, lambda, the per-time-point panels of k_hess_basis) is
+ * kept on the handle: further calls with the same pcof (bitwise), target, cost type, basis and grid skip it; every other
+ * evaluation entry point and every setter of those voids it.  Preconditions and refusals as qgd_eval_hessian, with the same
+ * codes; n_vec < 1 or NULL v / hv: QGD_ERR_ARGUMENT.  QGD_ERR_MEMORY is decided from this call's own buffers (about
+ * (2 n_ops order/2 + slab) panels per time point, independent of n_pcof).  Deterministic: the same bits on every run, and
+ * n_vec vectors give what n_vec single calls give.  DESIGN.md section 4d. */
+int qgd_eval_hessian_vec(qgd_handle h, const double *pcof, int32_t n_pcof, const double *v, int32_t n_vec, double *hv, double *grad);
+
 /* Operator path of the step-matrix and gradient kernels.  mode 0: automatic (sparse when every
  * row of the assembled Hamiltonian has at most min(16, N/2) entries and N <= 64 -- the drift +
  * a_k +/- a_k^dagger operators of src/multi_qudit_systems.jl -- else dense), 1: dense fp64 MFMA

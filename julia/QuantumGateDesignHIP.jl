@@ -295,6 +295,23 @@ function hip_eval_hessian(prob::SchrodingerProb, controls, pcof::Vector{Float64}
     return hess
 end
 
+# Exact Hessian-vector product(s) H v of the discrete objective by a second-order adjoint sweep (DESIGN.md section 4d): v a
+# vector or an n_pcof x k matrix; calls with the same pcof reuse what does not depend on v.
+function hip_eval_hessian_vec(prob::SchrodingerProb, controls, pcof::Vector{Float64}, v::VecOrMat{Float64},
+        target::AbstractMatrix{<:Number}; order::Int=2, cost_type=:Infidelity)
+    size(v, 1) == length(pcof) || throw(ArgumentError("v must have length(pcof) rows"))
+    dp = device_problem(prob, order)
+    pc_ptr, pc_len = set_controls!(dp, prob, controls, pcof)
+    set_cost_type!(dp, cost_type)
+    tr = Matrix{Float64}(vcat(real(target), imag(target)))
+    check(dp.handle, ccall((:qgd_set_target, libqgd), Cint, (Ptr{Cvoid}, Ptr{Float64}), dp.handle, tr))
+    hv = zeros(size(v))
+    GC.@preserve pcof check(dp.handle, ccall((:qgd_eval_hessian_vec, libqgd), Cint,
+          (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+          dp.handle, pc_ptr, pc_len, v, Int32(size(v, 2)), hv, C_NULL))
+    return hv
+end
+
 # ---- several GPUs: RCCL inside the library (include/qgd.h, "several GPUs behind ONE call") ------------------------------
 # One Julia process (or task pinned to a thread) per GPU.  Rank 0 makes the id; the host carries its 128 bytes to the
 # other ranks once (e.g. MPI.jl: `id = MPI.bcast(rank == 0 ? comm_unique_id() : nothing, 0, MPI.COMM_WORLD)`); after

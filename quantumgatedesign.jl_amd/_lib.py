@@ -24,7 +24,7 @@ EXPORTS = [
     "qgd_apply_hamiltonian", "qgd_get_intermediate", "qgd_get_timings",
     "qgd_set_partition", "qgd_get_partition", "qgd_set_stream", "qgd_exchange_buffer",
     "qgd_dist_forward_begin", "qgd_dist_forward_end", "qgd_dist_adjoint_begin", "qgd_dist_adjoint_end",
-    "qgd_dist_finish", "qgd_set_timing", "qgd_eval_adjoint", "qgd_set_operator_path", "qgd_get_operator_path", "qgd_eval_grad_forced", "qgd_eval_forward_forced", "qgd_eval_hessian",
+    "qgd_dist_finish", "qgd_set_timing", "qgd_eval_adjoint", "qgd_set_operator_path", "qgd_get_operator_path", "qgd_eval_grad_forced", "qgd_eval_forward_forced", "qgd_eval_hessian", "qgd_eval_hessian_vec",
     "qgd_register_host_buffer", "qgd_unregister_host_buffer", "qgd_create_csc", "qgd_cols_forward", "qgd_cols_adjoint",
     "qgd_set_lambda_derivatives", "qgd_set_cost_type",
     "qgd_comm_unique_id", "qgd_comm_init_rccl", "qgd_comm_destroy", "qgd_comm_info", "qgd_set_save_every",
@@ -107,6 +107,7 @@ def lib():
     L.qgd_set_timing.argtypes = [C.c_void_p, C.c_int32, C.c_char_p]
     L.qgd_eval_grad_forced.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.qgd_eval_hessian.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.qgd_eval_hessian_vec.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.qgd_eval_forward_forced.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.qgd_set_operator_path.argtypes = [C.c_void_p, C.c_int32]
     L.qgd_get_operator_path.argtypes = [C.c_void_p, C.c_void_p]

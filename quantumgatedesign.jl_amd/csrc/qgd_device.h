@@ -190,6 +190,16 @@ size_t qgdk_hess_slab(int Np, int m, int n_ops);
 int qgdk_hess_kernels(const qgdk_ctx *c, const double *shist, double *Z, double *half, double *slab, double *zt, double *Y);
 size_t qgdk_hess_gram_part(int n_pcof, int nt);
 int qgdk_hess_gram(const qgdk_ctx *c, const double *shist, double *ws, double *part, double *out);
+int qgdk_hess_basis(const qgdk_ctx *c, double *Z, double *half, double *slab);      /* k_hess_basis alone: Z and the halves of e_n */
+int qgdk_hess_wapply(const qgdk_ctx *c, const double *shist, double *ws, int n_dir);  /* ws = W s, general guard matrix */
+// exact Hessian-vector products (qgd_k_hvp.hip)
+size_t qgdk_hvp_gv_len(const qgdk_ctx *c);
+int qgdk_hvp_gv(const qgdk_ctx *c, const double *v, double *gvt);
+int qgdk_hvp_forced_sweep(const qgdk_ctx *c, const double *gvt, const void *one3, double *phi, double *bnd, double *sv);
+int qgdk_hvp_forcing(const qgdk_ctx *c, const double *Z, const double *half, const double *sv, const double *ws,
+                     const double *gvt, const double *term, double *F, double *part);
+int qgdk_hvp_adjoint(const qgdk_ctx *a);
+int qgdk_hvp_contract(const qgdk_ctx *c, const double *part, const double *gB, double *out);
 int qgdk_forcing_terms(const qgdk_ctx *c);
 int qgdk_forcing_add_derivs(const qgdk_ctx *c);
 int qgdk_forcing_sweep(const qgdk_ctx *c);

@@ -85,6 +85,19 @@ struct qgd_handle_s {
     std::vector<void *> hess_bufs;     // qgd_eval_hessian: sensitivity history and the work buffers of qgd_k_hessian.hip
     size_t hess_key = 0;               // (nt, n_pcof, basis directions, general guard) they were sized for
     double *hs_shist = nullptr, *hs_ws = nullptr, *hs_Z = nullptr, *hs_half = nullptr, *hs_slab = nullptr, *hs_zt = nullptr, *hs_Y = nullptr;
+    // qgd_eval_hessian_vec: the direction-independent setup of a product -- forward sweep, lambda, stage
+    // derivatives, the forced basis responses (in forced_bufs), Z and the halves of e_n -- stays on the handle.  hvp_valid: it
+    // belongs to the stored sweep (StoredSweep::pcof) and the present target, cost type, basis and grid; every transition of
+    // the sweep record clears it (hvp_void), as do the setters that free these buffers.
+    struct HvpBufs {
+        double *Z = nullptr, *half = nullptr, *slab = nullptr, *sv = nullptr, *ws = nullptr, *F = nullptr, *Y = nullptr, *mu = nullptr;
+        double *phi = nullptr, *bnd = nullptr, *gvt = nullptr, *term = nullptr, *part = nullptr, *v = nullptr, *gB = nullptr, *out = nullptr, *scal = nullptr;
+        void *one3 = nullptr;
+    } hv;
+    std::vector<void *> hvp_bufs;
+    size_t hvp_key = 0;                // (nt, n_pcof, basis directions, general guard, scan blocks) they were sized for
+    bool hvp_valid = false;
+    std::vector<double> hvp_grad;      // the adjoint gradient of the setup
     double *fsc_forced = nullptr, *fsc_forcing = nullptr;   // HBM work-panel slabs of the forced kernels when they exceed the LDS (N > 64)
     std::vector<void *> forcing_bufs;  // eval_forward with a user forcing
     size_t forcing_key = 0;
@@ -255,7 +268,8 @@ struct PhaseTimer {
 
 
 // The transitions of the StoredSweep record (described at its declaration).
-inline void sweep_void(qgd_handle h) { h->sweep.kind = SWEEP_NONE; h->sweep.derivs = false; }
+inline void hvp_void(qgd_handle h) { h->hvp_valid = false; }
+inline void sweep_void(qgd_handle h) { h->sweep.kind = SWEEP_NONE; h->sweep.derivs = false; hvp_void(h); }
 
 // a forward sweep is about to overwrite the buffers (after the checks that can refuse the call, before the first launch)
 inline void sweep_begin(qgd_handle h) { sweep_void(h); h->sweep.front = false; }
@@ -263,6 +277,7 @@ inline void sweep_begin(qgd_handle h) { sweep_void(h); h->sweep.front = false; }
 inline void sweep_done(qgd_handle h, SweepKind kind, const double *pcof, int n_pcof, bool gradient = false)
 {
     StoredSweep &s = h->sweep;
+    hvp_void(h);
     s.kind = kind;
     s.has_pcof = pcof != nullptr;
     if (pcof) s.pcof.assign(pcof, pcof + n_pcof); else s.pcof.clear();
@@ -273,7 +288,7 @@ inline void sweep_done(qgd_handle h, SweepKind kind, const double *pcof, int n_p
 }
 
 // a new target or cost type
-inline void sweep_terminal_changed(qgd_handle h) { if (h->sweep.kind == SWEEP_FRONT) h->sweep.reusable = false; }
+inline void sweep_terminal_changed(qgd_handle h) { if (h->sweep.kind == SWEEP_FRONT) h->sweep.reusable = false; hvp_void(h); }
 
 // the buffers hold a forward sweep that an adjoint sweep can differentiate
 inline bool sweep_stored(qgd_handle h) { return h->sweep.kind == SWEEP_GENERAL || h->sweep.kind == SWEEP_FRONT; }

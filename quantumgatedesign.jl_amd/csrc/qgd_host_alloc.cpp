@@ -183,6 +183,7 @@ int alloc_grid(qgd_handle h)
     free_pool(h->grid_bufs);
     free_pool(h->forced_bufs); h->forced_key = 0;
     free_pool(h->hess_bufs); h->hess_key = 0;
+    free_pool(h->hvp_bufs); h->hvp_key = 0; hvp_void(h);
     free_pool(h->forcing_bufs); h->forcing_key = 0;
     free_pool(h->stage_bufs); h->stage_hist = h->stage_lam = h->stage_f = nullptr;
     h->dlam = h->dlam_scratch = h->stage_lam_full = nullptr;
@@ -523,7 +524,7 @@ void qgd_destroy(qgd_handle h)
     if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
     for (auto &r : h->regs) (void)hipHostUnregister(r.host);
     free_pool(h->stage_bufs);
-    free_pool(h->static_bufs); free_pool(h->grid_bufs); free_pool(h->basis_bufs); free_pool(h->forced_bufs); free_pool(h->hess_bufs); free_pool(h->forcing_bufs);
+    free_pool(h->static_bufs); free_pool(h->grid_bufs); free_pool(h->basis_bufs); free_pool(h->forced_bufs); free_pool(h->hess_bufs); free_pool(h->hvp_bufs); free_pool(h->forcing_bufs);
     for (auto &p : h->phases) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     if (h->host_out) (void)hipHostFree(h->host_out);
     if (h->host_in) (void)hipHostFree(h->host_in);
@@ -585,6 +586,7 @@ int qgd_set_control_basis(qgd_handle h, const int32_t *n_coeff, const double *co
     free_pool(h->basis_bufs);
     free_pool(h->forced_bufs); h->forced_key = 0;
     free_pool(h->hess_bufs); h->hess_key = 0;
+    free_pool(h->hvp_bufs); h->hvp_key = 0; hvp_void(h);
     h->have_basis = false;
     sweep_void(h); h->sweep.has_pcof = false;
     k.scal = h->scal_static; k.grad = nullptr; k.redbuf = nullptr; if (h->status_static) k.status = h->status_static;
@@ -676,6 +678,7 @@ int qgd_set_control_tables(qgd_handle h, const double *pt, const double *qt)
         return QGD_OK;
     }
     h->tab_p_host.clear(); h->tab_q_host.clear();
+    hvp_void(h);      // (the kept setup of qgd_eval_hessian_vec reads the tables of its own pcof)
     const size_t cnt = (size_t)k.nt * (k.m + 1) * k.n_ops;
     double *tmp = nullptr;
     HIP_TRY(h, hipMalloc((void **)&tmp, 2 * cnt * sizeof(double) + 64));

@@ -1060,4 +1060,149 @@ int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *h
     return QGD_OK;
 }
 
+// buffers of qgd_eval_hessian_vec for the present grid, basis and guard kind (nothing depends on the number of parameters but
+// three vectors).  QGD_ERR_MEMORY is decided from what THIS call allocates: its own buffers and, when they are not there yet,
+// the forced gradient's basis responses.
+static int hvp_buffers(qgd_handle h)
+{
+    qgdk_ctx &k = h->k;
+    const size_t nt = k.nt, np = (size_t)k.n_pcof, NB = (size_t)k.n_ops * 2 * k.m, gpc = (size_t)k.cp / 8, B = (size_t)k.scan_blocks;
+    const size_t hstep = (size_t)k.Np * 2 * k.cp, hist = nt * hstep, n_ws = k.have_guard == 1 ? hist : 0;
+    const size_t key = ((((nt * 1000003u + np) * 4099u + NB) * 2u + (n_ws ? 1u : 0u)) * 1031u + B) | 1u;
+    if (h->hvp_key == key) return QGD_OK;
+    free_pool(h->hvp_bufs); h->hvp_key = 0; hvp_void(h);
+    const size_t n_Z = nt * NB * hstep, n_half = nt * gpc * NB * NB, n_slab = nt * gpc * qgdk_hess_slab(k.Np, k.m, k.n_ops);
+    const size_t n_gv = qgdk_hvp_gv_len(&k), n_part = nt * gpc * NB;
+    size_t bytes = (n_Z + n_half + n_slab + 4 * hist + n_ws + (2 * B + 1) * hstep + n_gv + hstep + n_part + 3 * np + 4 + 2) * sizeof(double);
+    (void)forced_buffers(h, nt, B, &bytes);
+    size_t fr = 0, tot = 0;
+    if ((h->mem_budget && bytes > h->mem_budget) || (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr))
+        return fail(h, QGD_ERR_MEMORY, "the buffers of qgd_eval_hessian_vec do not fit (" + std::to_string(bytes) + " bytes needed)");
+    auto &b = h->hv;
+    double *one3 = nullptr;
+    int rc;
+    if ((rc = dev_alloc(h, h->hvp_bufs, &b.Z, n_Z)) || (rc = dev_alloc(h, h->hvp_bufs, &b.half, n_half)) ||
+        (rc = dev_alloc(h, h->hvp_bufs, &b.slab, n_slab)) || (rc = dev_alloc(h, h->hvp_bufs, &b.sv, hist)) ||
+        (rc = dev_alloc(h, h->hvp_bufs, &b.F, hist)) || (rc = dev_alloc(h, h->hvp_bufs, &b.Y, hist)) ||
+        (rc = dev_alloc(h, h->hvp_bufs, &b.mu, hist)) || (n_ws && (rc = dev_alloc(h, h->hvp_bufs, &b.ws, n_ws))) ||
+        (rc = dev_alloc(h, h->hvp_bufs, &b.phi, B * hstep)) || (rc = dev_alloc(h, h->hvp_bufs, &b.bnd, (B + 1) * hstep)) ||
+        (rc = dev_alloc(h, h->hvp_bufs, &b.gvt, n_gv)) || (rc = dev_alloc(h, h->hvp_bufs, &b.term, hstep)) ||
+        (rc = dev_alloc(h, h->hvp_bufs, &b.part, n_part)) || (rc = dev_alloc(h, h->hvp_bufs, &b.v, np)) ||
+        (rc = dev_alloc(h, h->hvp_bufs, &b.gB, np)) || (rc = dev_alloc(h, h->hvp_bufs, &b.out, np)) ||
+        (rc = dev_alloc(h, h->hvp_bufs, &b.scal, (size_t)4)) || (rc = dev_alloc(h, h->hvp_bufs, &one3, (size_t)2))) {
+        free_pool(h->hvp_bufs);
+        return rc;
+    }
+    if (!n_ws) b.ws = nullptr;
+    b.one3 = one3;
+    // s_v(0) = 0 and mu_0 = 0 are never written again; the unused (M+1)-th Taylor slot of the direction table stays zero
+    const struct { int64_t goff; int32_t ncoef, poff; } one = {0, 1, 0};      // the one-operator, one-coefficient basis of the direction table
+    HIP_TRY(h, hipMemcpyAsync(one3, &one, sizeof(one), hipMemcpyHostToDevice, k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.sv, 0, hist * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.mu, 0, hist * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.Y, 0, hist * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.bnd, 0, (B + 1) * hstep * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.gvt, 0, n_gv * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.scal, 0, 4 * sizeof(double), k.stream));
+    HIP_TRY(h, hipStreamSynchronize(k.stream));      // (`one` leaves scope)
+    h->hvp_key = key;
+    return QGD_OK;
+}
+
+
+// Phi'' s_v(N) as the terminal part of the second-order adjoint's right-hand side F = -f, in panel layout:
+//   :Infidelity  +(2/N_ess^2) (<s_v,R> R + <s_v,T> T)  (forced_terminal's overlaps);   :Tracking / :Norm  -s_v(N)
+static int hvp_terminal(qgd_handle h, const double *svN_dev, double *term_dev)
+{
+    qgdk_ctx &k = h->k;
+    const size_t N = k.N, PWc = 2 * (size_t)k.cp, hstep = (size_t)k.Np * PWc, L = 2 * N * k.c;
+    std::vector<double> sN(hstep), s(L), t(L), out(hstep, 0.0);
+    HIP_TRY(h, hipMemcpyAsync(sN.data(), svN_dev, hstep * sizeof(double), hipMemcpyDeviceToHost, k.stream));
+    HIP_TRY(h, hipStreamSynchronize(k.stream));
+    unpack_panel(s.data(), 2 * N, sN.data(), (int)PWc, k.N, k.c);
+    if (k.cost_type) {
+        for (size_t e = 0; e < L; e++) t[e] = -s[e];
+    } else {
+        double sR = 0.0, sT = 0.0;
+        for (size_t col = 0; col < (size_t)k.c; col++)
+            for (size_t i = 0; i < N; i++) {
+                const size_t e = i + 2 * N * col;
+                const double sre = s[e], sim = s[N + e], rre = h->target_host[e], rim = h->target_host[N + e];
+                sR += sre * rre + sim * rim;
+                sT += sre * rim - sim * rre;
+            }
+        const double f = 2.0 / ((double)k.n_ess * k.n_ess);
+        for (size_t col = 0; col < (size_t)k.c; col++)
+            for (size_t i = 0; i < N; i++) {
+                const size_t e = i + 2 * N * col;
+                const double rre = h->target_host[e], rim = h->target_host[N + e];
+                t[e] = f * (sR * rre + sT * rim);            // T = [R_im; -R_re]
+                t[N + e] = f * (sR * rim - sT * rre);
+            }
+    }
+    pack_panel(out.data(), (int)PWc, t.data(), k.N, k.c, 2 * N);
+    HIP_TRY(h, hipMemcpyAsync(term_dev, out.data(), hstep * sizeof(double), hipMemcpyHostToDevice, k.stream));
+    HIP_TRY(h, hipStreamSynchronize(k.stream));      // (`out` leaves scope)
+    return QGD_OK;
+}
+
+
+// exact Hessian-vector products.  Setup, once per pcof and kept on the handle: forward sweep, lambda,
+// stage derivatives, forced basis responses, k_hess_basis.  Per vector: the direction table, one forced sweep, k_hvp_forcing,
+// the adjoint sweep with that forcing (mu), the gradient kernels with mu in place of lambda, k_hvp_contract.
+int qgd_eval_hessian_vec(qgd_handle h, const double *pcof, int32_t n_pcof, const double *v, int32_t n_vec, double *hv, double *grad)
+{
+    if (h) drop_graph(h);
+    if (!h || !v || !hv) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    if (n_vec < 1) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_hessian_vec needs at least one vector");
+    HIP_TRY(h, hipSetDevice(h->device));
+    NEED_GRID(h);
+    qgdk_ctx &k = h->k;
+    if (h->part_world != 1 || h->comm) return fail(h, QGD_ERR_STATE, "partitioned handle: the Hessian-vector product is single-GPU");
+    if (!k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before qgd_eval_hessian_vec");
+    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_eval_hessian_vec");
+    if (!pcof) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian_vec needs pcof: with control tables set directly the second derivative of the controls is unknown");
+    if (n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
+    if (h->chunks_eff > 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian_vec needs the whole time grid resident (this handle processes it in windows)");
+    if (k.N > 64) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian_vec supports N <= 64");
+    if (k.n_ops < 1 || k.n_ops * 2 * k.m > 64) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian_vec needs 1 <= 2 * n_ops * order/2 <= 64 basis directions");
+    const size_t nt = k.nt, np = (size_t)k.n_pcof, hstep = (size_t)k.Np * 2 * k.cp;
+    int rc;
+    if ((rc = hvp_buffers(h))) return rc;
+    auto &b = h->hv;
+    if (!(h->hvp_valid && h->sweep.kind == SWEEP_GENERAL && sweep_reusable(h, pcof, n_pcof))) {
+        if ((rc = run_forward(h, pcof, n_pcof))) return rc;      // (the general two-point path, as qgd_eval_hessian)
+        if ((rc = adjoint_begin(h))) return rc;                  // lambda and the adjoint gradient
+        if ((rc = adjoint_end(h))) return rc;
+        if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
+        if ((rc = forced_buffers(h, nt, k.scan_blocks))) return rc;
+        { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); }
+        { PhaseTimer t(h, "hess_basis"); K_TRY(h, qgdk_hess_basis(&k, b.Z, b.half, b.slab)); }
+        if ((rc = check_status(h))) return rc;
+        h->hvp_grad.resize(np);
+        HIP_TRY(h, hipMemcpyAsync(h->hvp_grad.data(), k.grad, np * sizeof(double), hipMemcpyDeviceToHost, k.stream));
+        HIP_TRY(h, hipStreamSynchronize(k.stream));
+        h->hvp_valid = true;
+    }
+    // the second-order adjoint runs on a copy of the context: its forcing, y and mu in the product's own buffers, so that
+    // lambda, the guard forcing and the scalars of the kept evaluation stay as they are for the next vector
+    qgdk_ctx a = k;
+    a.forcing = b.F; a.yhist = b.Y; a.lam = b.mu; a.grad = b.gB; a.scal = b.scal;
+    a.front = 0; a.fuse_terminal = 0; a.grad_accumulate = 0; a.mirror_dev = nullptr; a.mirror_ticket = nullptr;
+    for (int32_t j = 0; j < n_vec; j++) {
+        HIP_TRY(h, hipMemcpyAsync(b.v, v + (size_t)j * np, np * sizeof(double), hipMemcpyHostToDevice, k.stream));
+        { PhaseTimer t(h, "hvp_direction"); K_TRY(h, qgdk_hvp_gv(&k, b.v, b.gvt)); }
+        { PhaseTimer t(h, "hvp_sweep"); K_TRY(h, qgdk_hvp_forced_sweep(&k, b.gvt, b.one3, b.phi, b.bnd, b.sv)); }
+        if (k.have_guard == 1) { PhaseTimer t(h, "hvp_guard"); K_TRY(h, qgdk_hess_wapply(&k, b.sv, b.ws, 1)); }
+        if ((rc = hvp_terminal(h, b.sv + (nt - 1) * hstep, b.term))) return rc;
+        { PhaseTimer t(h, "hvp_forcing"); K_TRY(h, qgdk_hvp_forcing(&k, b.Z, b.half, b.sv, b.ws, b.gvt, b.term, b.F, b.part)); }
+        { PhaseTimer t(h, "hvp_adjoint"); K_TRY(h, qgdk_hvp_adjoint(&a)); }
+        { PhaseTimer t(h, "hvp_gradient"); K_TRY(h, qgdk_gradient(&a)); K_TRY(h, qgdk_hvp_contract(&k, b.part, b.gB, b.out)); }
+        HIP_TRY(h, hipMemcpyAsync(hv + (size_t)j * np, b.out, np * sizeof(double), hipMemcpyDeviceToHost, k.stream));
+        HIP_TRY(h, hipStreamSynchronize(k.stream));
+    }
+    if (grad) memcpy(grad, h->hvp_grad.data(), np * sizeof(double));
+    return QGD_OK;
+}
+
 }  // extern "C"

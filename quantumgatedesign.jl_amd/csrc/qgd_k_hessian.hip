@@ -318,20 +318,34 @@ extern "C" {
 
 size_t qgdk_hess_slab(int Np, int m, int n_ops) { return hess_slab(Np, m, n_ops); }
 
-int qgdk_hess_kernels(const qgdk_ctx *c, const double *shist, double *Z, double *half, double *slab, double *zt, double *Y)
+// k_hess_basis alone: Z and the half-matrices of e_n depend on pcof only, not on the direction a Hessian is applied to
+// (qgd_eval_hessian_vec keeps them on the handle)
+int qgdk_hess_basis(const qgdk_ctx *c, double *Z, double *half, double *slab)
 {
-    const int NB = c->n_ops * 2 * c->m, gnt = c->g_nt ? c->g_nt : c->nt;
-    if (NB > 64) return -1;      // (k_hess_sigma keeps sigma^s of one parameter in 64 LDS slots)
+    if (c->n_ops * 2 * c->m > 64) return -1;      // (k_hess_sigma / k_hvp_forcing keep one value per direction in 64 LDS slots)
 #define CALL_HB(NO) hipLaunchKernelGGL((k_hess_basis<NO>), dim3(c->cp / 8, c->nt), dim3(256), 0, c->stream, c->ops, c->tab, c->hist, \
                                        c->dpsi, c->lam, c->cw, Z, half, slab, c->Np, c->N, c->cp, c->n_ops, c->m, c->nt)
     DISPATCH_NOPS(c->n_ops, CALL_HB)
 #undef CALL_HB
-    HIPCHK(hipGetLastError());
+    return (int)hipGetLastError();
+}
+
+int qgdk_hess_kernels(const qgdk_ctx *c, const double *shist, double *Z, double *half, double *slab, double *zt, double *Y)
+{
+    const int NB = c->n_ops * 2 * c->m, gnt = c->g_nt ? c->g_nt : c->nt;
+    HIPCHK((hipError_t)qgdk_hess_basis(c, Z, half, slab));
     hipLaunchKernelGGL(k_hess_sigma, dim3(c->n_pcof, c->nt), dim3(256), 0, c->stream, shist, Z, half, c->G, c->goff, c->ncoef, c->poff,
                        zt, c->Np, c->cp, c->n_pcof, NB, c->m, gnt);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_hess_contract, dim3(c->n_pcof), dim3(256), 0, c->stream, zt, c->G, c->goff, c->ncoef, c->poff, Y,
                        c->n_pcof, c->n_ops, c->m, c->nt, gnt);
+    return (int)hipGetLastError();
+}
+
+// ws = W s for n_dir sensitivity directions side by side (general guard matrix)
+int qgdk_hess_wapply(const qgdk_ctx *c, const double *shist, double *ws, int n_dir)
+{
+    hipLaunchKernelGGL(k_hess_wapply, dim3(n_dir * (c->cp / 8), c->nt), dim3(256), 0, c->stream, c->guard, shist, ws, c->Np, c->N, 2 * n_dir * c->cp);
     return (int)hipGetLastError();
 }
 

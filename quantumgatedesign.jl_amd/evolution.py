@@ -426,6 +426,25 @@ class DeviceProblem:
         _lib.check(self.h, self.lib.qgd_eval_hessian(self.h, _vp(pcof), len(pcof), _vp(hess), None if grad is None else _vp(grad)))
         return hess
 
+    def eval_hessian_vec(self, pcof, v, grad=None):
+        """Exact Hessian-vector product(s) H v at pcof by a second-order adjoint sweep, without forming
+        H.  ``v``: (n_pcof,) or (n_pcof, k); the result has the same shape.  ``grad``: an optional float64 array of n_pcof that
+        receives the adjoint gradient.  What does not depend on v stays on the handle: further calls with the same pcof cost
+        one forced sweep with a single direction and one adjoint sweep each.  Needs controls linear in pcof and the target."""
+        if getattr(self, "_general", None):
+            raise NotImplementedError("eval_hessian_vec needs controls that are linear in pcof (is_linear = True)")
+        pcof = np.ascontiguousarray(pcof, dtype=np.float64)
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim not in (1, 2) or v.shape[0] != len(pcof):
+            raise ValueError(f"v must have shape ({len(pcof)},) or ({len(pcof)}, k)")
+        cols = np.asfortranarray(v.reshape(len(pcof), -1))
+        hv = np.zeros(cols.shape, order="F")
+        if grad is not None:
+            _check_out(grad, (len(pcof),), "grad")
+        _lib.check(self.h, self.lib.qgd_eval_hessian_vec(self.h, _vp(pcof), len(pcof), _vp(cols) if cols.size else None, cols.shape[1],
+                                                          _vp(hv) if hv.size else None, None if grad is None else _vp(grad)))
+        return hv.reshape(v.shape) if v.ndim == 1 else np.ascontiguousarray(hv)
+
     def set_operator_path(self, mode):
         """"auto" | "dense" (fp64 MFMA kernels) | "sparse" (ELL kernels; raises if the operators do not qualify)."""
         code = {"auto": 0, "dense": 1, "sparse": 2}[mode]
@@ -557,6 +576,23 @@ def eval_grad_forced(prob, controls, pcof, target, order=2, cost_type="Infidelit
     dp.set_cost_type(cost_type)
     try:
         return dp.eval_grad_forced(pcof)
+    finally:
+        dp.set_cost_type("Infidelity")
+
+
+def eval_hessian_vec(prob, controls, pcof, v, target, order=2, cost_type="Infidelity"):
+    """Exact Hessian-vector product(s) of the discrete objective: ``eval_hessian(...) @ v`` without the Hessian (DESIGN.md
+    section 4d).  ``v``: (n_pcof,) or (n_pcof, k).  Calls with the same pcof (and problem, controls, target, cost type) reuse
+    the part that does not depend on v.  Controls linear in pcof."""
+    cl = controls if isinstance(controls, (list, tuple)) else [controls]
+    if not all(getattr(c, "is_linear", False) for c in cl):
+        raise NotImplementedError("eval_hessian_vec needs controls that are linear in pcof (is_linear = True)")
+    dp = device_problem(prob, order)
+    dp.set_controls(controls)
+    dp.set_target(target)
+    dp.set_cost_type(cost_type)
+    try:
+        return dp.eval_hessian_vec(np.asarray(pcof, dtype=np.float64), v)
     finally:
         dp.set_cost_type("Infidelity")
 
