@@ -163,6 +163,28 @@ int qgd_eval_forward(qgd_handle h, const double *pcof, int32_t n_pcof,
  * discrete_adjoint! has no such keyword.  Default 1. */
 int qgd_set_save_every(qgd_handle h, int32_t save_every_nsteps);
 
+/* The state trajectory alone, and what one looks at after a forward run: the level populations along the sweep
+ * (get_populations, src/state_vector_helpers.jl:10-52, which the reference applies to a downloaded uv_history).  Both run the
+ * forward sweep as the call above does, form no stage derivatives and download nothing but their output; both honour
+ * qgd_set_save_every (n_slots = 1 + nsteps / s), take pcof == NULL when tables were set directly, fill out3 (nullable) as
+ * the call above, accept registered and unregistered output arrays, work on resident and windowed time grids
+ * (qgd_set_memory_budget: the output is filled window by window) and leave the stored forward sweep as the call above without
+ * an output array leaves it, so that a history_precomputed gradient call with the same pcof may follow.
+ *   states       [2N, n_slots, n_cols]: Taylor index 0 of uv_history, the same bits.  forcing (nullable): the forced sweep of
+ *                qgd_eval_forward_forced further down, with its forcing layout and its limits.
+ *   populations  [N, n_slots, n_cols]: p[k, s, col] = u_k^2 + v_k^2 (level_map NULL, n_groups ignored), or
+ *                [n_groups, n_slots, n_cols]: sum_k level_map[g, k] p[k, s, col] with level_map[n_groups x N] column-major
+ *                (e.g. the 0/1 map of per-qudit level populations), summed over k in ascending order on the device: the same
+ *                bits on every run.  history_precomputed != 0: the device's stored forward sweep is reused under the rule of
+ *                the gradient call below (same pcof bitwise, else the sweep is redone; a windowed grid always redoes it;
+ *                QGD_ERR_STATE when there is no previous forward evaluation).
+ * QGD_ERR_ARGUMENT, before anything is launched: NULL output, level_map given with n_groups < 1.  QGD_ERR_UNSUPPORTED: a
+ * handle with a communicator or a partition (these two calls are single-GPU). */
+int qgd_eval_states(qgd_handle h, const double *pcof, int32_t n_pcof, const double *forcing,
+                    double *states, double *out3);
+int qgd_eval_populations(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
+                         const double *level_map, int32_t n_groups, double *populations, double *out3);
+
 /* discrete_adjoint! (eval_grad_discrete_adjoint.jl:107-160): gradient of
  * infidelity + guard penalty (no ridge term, as the reference).  With
  * history_precomputed != 0 the forward sweep of the last evaluation is reused

@@ -199,6 +199,48 @@ function hip_eval_forward!(uv_history::Array{Float64,4}, prob::SchrodingerProb, 
     return nothing      # (as the reference; the three scalars: last_objective(prob, order))
 end
 
+"The state trajectory alone, real form [2N, 1+div(nsteps,s), N_initial_conditions] = uv_history[:, 1, :, :] of
+hip_eval_forward! (the same bits): no stage derivatives are formed or moved (qgd_eval_states).  Single-GPU handles."
+function hip_eval_states(prob::SchrodingerProb, controls, pcof::Vector{Float64}; order::Int=2, saveEveryNsteps::Int=1)
+    dp = device_problem(prob, order)
+    set_cost_type!(dp, :Infidelity)
+    pc_ptr, pc_len = set_controls!(dp, prob, controls, pcof)
+    states = zeros(2 * prob.N_tot_levels, 1 + div(prob.nsteps, saveEveryNsteps), prob.N_initial_conditions)
+    check(dp.handle, ccall((:qgd_set_save_every, libqgd), Cint, (Ptr{Cvoid}, Int32), dp.handle, saveEveryNsteps))
+    try
+        GC.@preserve pcof check(dp.handle, ccall((:qgd_eval_states, libqgd), Cint,
+              (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              dp.handle, pc_ptr, pc_len, C_NULL, states, dp.last_out3))
+    finally
+        ccall((:qgd_set_save_every, libqgd), Cint, (Ptr{Cvoid}, Int32), dp.handle, 1)
+    end
+    return states
+end
+
+"get_populations (src/state_vector_helpers.jl:10-52) without the history on the host: the level populations
+[N, 1+div(nsteps,s), N_initial_conditions] of the forward sweep, formed on the device (qgd_eval_populations) -- or, with
+`level_map` [n_groups, N], level_map * populations[:, n, i] for every (n, i): [n_groups, ...] (per-qudit level populations:
+the 0/1 map of the subsystems).  history_precomputed: reuse the device's forward sweep when it belongs to this pcof."
+function hip_get_populations(prob::SchrodingerProb, controls, pcof::Vector{Float64}; order::Int=2, saveEveryNsteps::Int=1,
+                             level_map::Union{Nothing,Matrix{Float64}}=nothing, history_precomputed::Bool=false)
+    dp = device_problem(prob, order)
+    set_cost_type!(dp, :Infidelity)
+    pc_ptr, pc_len = set_controls!(dp, prob, controls, pcof)
+    level_map === nothing || size(level_map, 2) == prob.N_tot_levels || throw(DimensionMismatch("level_map must be [n_groups, $(prob.N_tot_levels)]"))
+    rows = level_map === nothing ? prob.N_tot_levels : size(level_map, 1)
+    populations = zeros(rows, 1 + div(prob.nsteps, saveEveryNsteps), prob.N_initial_conditions)
+    check(dp.handle, ccall((:qgd_set_save_every, libqgd), Cint, (Ptr{Cvoid}, Int32), dp.handle, saveEveryNsteps))
+    try
+        GC.@preserve pcof level_map check(dp.handle, ccall((:qgd_eval_populations, libqgd), Cint,
+              (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+              dp.handle, pc_ptr, pc_len, history_precomputed ? 1 : 0, level_map === nothing ? C_NULL : pointer(level_map),
+              level_map === nothing ? 0 : rows, populations, dp.last_out3))
+    finally
+        ccall((:qgd_set_save_every, libqgd), Cint, (Ptr{Cvoid}, Int32), dp.handle, 1)
+    end
+    return populations
+end
+
 "(infidelity, guard penalty) of the last evaluation of (prob, order) -- with :Tracking / :Norm: (cost, guard penalty)."
 function last_objective(prob::SchrodingerProb, order::Integer)
     dp = device_problem(prob, order)

@@ -227,6 +227,10 @@ int qgdk_flag_to_scal(const qgdk_ctx *c);   /* scal[3] = 1.0 when the singularit
 int qgdk_layout(const qgdk_ctx *c, const double *panels, long long src_n, long long src_j, double *ref,
                 long long dst_col, long long dst_n, long long dst_j, int n0, int n_cnt, int j_cnt,
                 int to_panels, hipStream_t stream, int max_workgroups);
+/* qgd_k_observe.hip: state panels of n_cnt output slots (src_n doubles apart) -> out[col][slot][rows], rows = N level populations
+   u^2 + v^2 (map_dev null) or n_groups sums over the levels weighted by map_dev[n_groups x N] (column-major, fixed order) */
+int qgdk_populations(const qgdk_ctx *c, const double *panels, long long src_n, double *out, long long dst_col,
+                     long long dst_n, int n_cnt, const double *map_dev, int n_groups, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

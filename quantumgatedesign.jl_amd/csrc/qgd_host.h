@@ -141,6 +141,10 @@ struct qgd_handle_s {
     std::vector<HostReg> regs;
     std::vector<void *> stage_bufs;
     double *stage_hist = nullptr, *stage_lam = nullptr, *stage_f = nullptr;
+    // qgd_eval_states / qgd_eval_populations: compact staging buffer [rows, slots, c] and the caller's level map on the device
+    // (both in stage_bufs, grown to the largest request so far)
+    double *stage_obs = nullptr, *obs_map = nullptr;
+    size_t stage_obs_len = 0, obs_map_len = 0;
     // qgd_set_lambda_derivatives: the m derivative columns of lambda_history as the reference leaves them
     bool lambda_derivs = false;
     double *dlam = nullptr, *dlam_scratch = nullptr, *stage_lam_full = nullptr;
@@ -350,6 +354,11 @@ struct RcclApi {
 
 RcclApi &rccl();
 
+// What qgd_eval_states / qgd_eval_populations take out of the state panels of a sweep: the states themselves [2N, slots, c],
+// the level populations [N, slots, c] (n_groups = 0) or their contraction with the level map on the device [n_groups, slots, c]
+enum ObserveKind { OBS_STATES, OBS_POPULATIONS };
+struct Observe { ObserveKind kind; int n_groups; double *out; };
+
 // qgd_host_alloc.cpp
 void free_pool(std::vector<void *> &pool);
 void drop_graph(qgd_handle h);
@@ -365,6 +374,7 @@ int download(qgd_handle h, void *dst, const void *src, size_t row_bytes, size_t 
 int copy_history_out(qgd_handle h, double *uv_history, int save = 1);
 int copy_panels_out(qgd_handle h, const double *panels, double **stage, double *out, size_t J, int n_first);
 int copy_lambda_full_out(qgd_handle h, double *out);
+int observe_out(qgd_handle h, const Observe &obs, int save);
 int upload_pcof(qgd_handle h, const double *pcof, int n_pcof);
 int forward_begin(qgd_handle h, const double *pcof, int n_pcof, bool allow_front = false);
 int forward_end(qgd_handle h);
@@ -377,7 +387,7 @@ int window_lambda_full_out(qgd_handle h, double *out);
 int window_panels_out(qgd_handle h, const double *panels, double **stage, double *out, size_t J, int n_first);
 int enter_window(qgd_handle h, const double *pcof, int r, bool with_start_state);
 int chunk_forward(qgd_handle h, const double *pcof, int n_pcof, int r, bool rerun);
-int chunked_forward(qgd_handle h, const double *pcof, int n_pcof, double *uv_history = nullptr, int save = 1);
+int chunked_forward(qgd_handle h, const double *pcof, int n_pcof, double *uv_history = nullptr, int save = 1, const Observe *obs = nullptr);
 int chunked_adjoint(qgd_handle h, double *lambda_history = nullptr, double *adjoint_forcing = nullptr);
 int forcing_buffers(qgd_handle h, size_t nt, size_t B);
 int upload_forcing(qgd_handle h, const double *forcing, size_t nt, size_t n_off);

@@ -148,6 +148,58 @@ int copy_lambda_full_out(qgd_handle h, double *out)
 }
 
 
+// a staging buffer of stage_bufs that grows to the largest request (the copies that read the old one were awaited by the
+// call that issued them)
+static int grow_stage(qgd_handle h, double **p, size_t *len, size_t need)
+{
+    if (*p && *len >= need) return QGD_OK;
+    if (*p) {
+        auto it = std::find(h->stage_bufs.begin(), h->stage_bufs.end(), (void *)*p);
+        if (it != h->stage_bufs.end()) h->stage_bufs.erase(it);
+        (void)hipFree(*p);
+        *p = nullptr; *len = 0;
+    }
+    int rc = dev_alloc(h, h->stage_bufs, p, need);
+    if (!rc) *len = need;
+    return rc;
+}
+
+
+// qgd_eval_states / qgd_eval_populations: the state panels hist [nt][Np][2cp] of the grid -- or of the window of a windowed
+// grid that is in the buffers -- -> the caller's [rows, 1 + (nt_glob-1)/save, c] at the window's slots, rows = 2N (the states:
+// Taylor index 0 of uv_history, through the same re-layout kernel), N (level populations) or n_groups (populations contracted
+// with the level map in obs_map).  No stage derivatives, a staging buffer of exactly the bytes that leave.  Resident grid:
+// asynchronous like copy_history_out (finish_copies() before returning); a window's copy is awaited here, like
+// window_history_out's, before the next window overwrites the panels.
+int observe_out(qgd_handle h, const Observe &obs, int save)
+{
+    qgdk_ctx &k = h->k;
+    const size_t hstep = (size_t)k.Np * 2 * k.cp, ntg = (size_t)k.nt_glob, sv = (size_t)save;
+    const size_t rows = obs.kind == OBS_STATES ? 2 * (size_t)k.N : (obs.n_groups > 0 ? (size_t)obs.n_groups : (size_t)k.N);
+    // slot s of the output holds GLOBAL time point s * save; the buffers hold the points n_off .. n_off + nt - 1
+    const size_t g_lo = (size_t)k.n_off, g_hi = (size_t)k.n_off + (size_t)k.nt - 1;
+    const size_t s_lo = (g_lo + sv - 1) / sv, s_hi = g_hi / sv;
+    if (s_hi < s_lo) return QGD_OK;                                                  // (no saved point falls into this window)
+    const size_t cnt = s_hi - s_lo + 1, loc = s_lo * sv - g_lo, slots = 1 + (ntg - 1) / sv;
+    int rc = copy_side(h);
+    if (rc) return rc;
+    if ((rc = grow_stage(h, &h->stage_obs, &h->stage_obs_len, rows * cnt * k.c))) return rc;
+    const double *src = k.hist + loc * hstep;
+    if (obs.kind == OBS_STATES) {
+        K_TRY(h, qgdk_layout(&k, src, (long long)(hstep * sv), 0, h->stage_obs, (long long)(cnt * rows), (long long)rows, 0, 0, (int)cnt, 1, 0, k.stream, 0));
+    } else {
+        PhaseTimer t(h, "populations");
+        K_TRY(h, qgdk_populations(&k, src, (long long)(hstep * sv), h->stage_obs, (long long)(cnt * rows), (long long)rows, (int)cnt,
+                                  obs.n_groups > 0 ? h->obs_map : nullptr, obs.n_groups, k.stream));
+    }
+    if ((rc = hand_over(h))) return rc;
+    if (h->chunks_eff == 1) return download(h, obs.out, h->stage_obs, rows * sizeof(double), cnt * k.c);      // (cnt == slots)
+    const size_t row = cnt * rows * sizeof(double);
+    HIP_TRY(h, hipMemcpy2DAsync(obs.out + s_lo * rows, slots * rows * sizeof(double), h->stage_obs, row, row, (size_t)k.c, hipMemcpyDeviceToHost, h->copy_stream));
+    return finish_copies(h);
+}
+
+
 int upload_pcof(qgd_handle h, const double *pcof, int n_pcof)
 {
     const double *src = pcof;
@@ -537,8 +589,9 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, int32
 // forced state the previous one ended in, with its slice of the caller's forcing; the guard penalty accumulates over the
 // windows, the overlaps come from the final state; uv_history (stage derivatives w_j = D_j w_0 + E_j included) window by
 // window as in chunked_forward.
-int qgd_eval_forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, const double *forcing,
-                            double *uv_history, double *out3)
+// (states: qgd_eval_states with a forcing -- the forced states alone, no stage derivatives)
+static int forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, const double *forcing,
+                          double *uv_history, double *states, double *out3)
 {
     if (h) drop_graph(h);
     if (!h || !forcing) return fail(h, QGD_ERR_ARGUMENT, "null argument");
@@ -580,10 +633,74 @@ int qgd_eval_forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, co
             K_TRY(h, qgdk_forcing_add_derivs(&k));     // w_j = D_j w_0 + E_j
             if ((rc = W > 1 ? window_history_out(h, uv_history, h->save_every) : copy_history_out(h, uv_history, h->save_every))) return rc;
         }
+        if (states && (rc = observe_out(h, Observe{OBS_STATES, 0, states}, h->save_every))) return rc;
     }
     { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target)); }
     if ((rc = fetch_results(h, nullptr, out3))) { (void)finish_copies(h); return rc; }
     return finish_copies(h);
+}
+
+
+int qgd_eval_forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, const double *forcing,
+                            double *uv_history, double *out3)
+{
+    return forward_forced(h, pcof, n_pcof, forcing, uv_history, nullptr, out3);
+}
+
+
+// The forward sweep (or, history_precomputed under the rule of qgd_discrete_adjoint, the stored one) and nothing of it but what
+// `obs` names.  The sweep record ends as qgd_eval_forward without an output array leaves it.
+static int observe_eval(qgd_handle h, const double *pcof, int n_pcof, int history_precomputed, const Observe &obs, double *out3)
+{
+    qgdk_ctx &k = h->k;
+    int rc;
+    if (history_precomputed && h->sweep.kind == SWEEP_NONE)
+        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+    if (h->chunks_eff > 1) {      // one window is resident at a time: the pass over the windows is redone, each hands out its share
+        if ((rc = chunked_forward(h, pcof, n_pcof, nullptr, h->save_every, &obs))) return rc;
+        return fetch_results(h, nullptr, out3);
+    }
+    struct CopyGuard { qgd_handle h; ~CopyGuard() { (void)finish_copies(h); } } guard{h};      // no copy outlives the call
+    if (history_precomputed && sweep_reusable(h, pcof, n_pcof)) {
+        // (the overlaps in out3 belong to the present target, which may have been set after the sweep)
+        PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target));
+    } else if ((rc = run_forward(h, pcof, n_pcof, true))) return rc;
+    if ((rc = observe_out(h, obs, h->save_every))) return rc;
+    if ((rc = fetch_results(h, nullptr, out3))) return rc;
+    return finish_copies(h);
+}
+
+
+int qgd_eval_states(qgd_handle h, const double *pcof, int32_t n_pcof, const double *forcing, double *states, double *out3)
+{
+    if (!h) return QGD_ERR_ARGUMENT;
+    if (!states) return fail(h, QGD_ERR_ARGUMENT, "null output array");
+    HIP_TRY(h, hipSetDevice(h->device));
+    NEED_GRID(h);
+    if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_states is single-GPU: this handle has a communicator or a partition");
+    if (forcing) return forward_forced(h, pcof, n_pcof, forcing, nullptr, states, out3);
+    return observe_eval(h, pcof, n_pcof, 0, Observe{OBS_STATES, 0, states}, out3);
+}
+
+
+int qgd_eval_populations(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
+                         const double *level_map, int32_t n_groups, double *populations, double *out3)
+{
+    if (!h) return QGD_ERR_ARGUMENT;
+    if (!populations) return fail(h, QGD_ERR_ARGUMENT, "null output array");
+    if (level_map && n_groups < 1) return fail(h, QGD_ERR_ARGUMENT, "a level map needs n_groups >= 1");
+    HIP_TRY(h, hipSetDevice(h->device));
+    NEED_GRID(h);
+    if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_populations is single-GPU: this handle has a communicator or a partition");
+    if (history_precomputed && h->sweep.kind == SWEEP_NONE)
+        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+    if (level_map) {
+        const size_t len = (size_t)n_groups * h->k.N;
+        int rc = grow_stage(h, &h->obs_map, &h->obs_map_len, len);
+        if (rc) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->obs_map, level_map, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
+    }
+    return observe_eval(h, pcof, n_pcof, history_precomputed, Observe{OBS_POPULATIONS, level_map ? n_groups : 0, populations}, out3);
 }
 
 

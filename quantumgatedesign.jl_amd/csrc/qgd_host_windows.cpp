@@ -162,7 +162,7 @@ int chunk_forward(qgd_handle h, const double *pcof, int n_pcof, int r, bool reru
 }
 
 
-int chunked_forward(qgd_handle h, const double *pcof, int n_pcof, double *uv_history, int save)
+int chunked_forward(qgd_handle h, const double *pcof, int n_pcof, double *uv_history, int save, const Observe *obs)
 {
     qgdk_ctx &k = h->k;
     if (!pcof && !h->have_tables && k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
@@ -173,6 +173,7 @@ int chunked_forward(qgd_handle h, const double *pcof, int n_pcof, double *uv_his
             { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
             if ((rc = window_history_out(h, uv_history, save))) return rc;
         }
+        if (obs && (rc = observe_out(h, *obs, save))) return rc;      // states or populations of the window, nothing else
     }
     { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target)); }      // overlaps (and y_N) from the final state
     sweep_done(h, SWEEP_GENERAL, pcof, n_pcof);

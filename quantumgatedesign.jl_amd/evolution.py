@@ -8,6 +8,8 @@ behaviour as the reference:
   discrete_adjoint_(grad, history, lambda_history, adjoint_forcing, prob, controls, pcof, target;
                     order, history_precomputed)                   eval_grad_discrete_adjoint.jl:107-160
   infidelity(...), infidelity_real, guard_penalty_real            infidelity.jl:7-96
+  get_populations(history)                                        state_vector_helpers.jl:10-52
+  eval_populations(prob, controls, pcof; order, saveEveryNsteps, level_map)   the same populations, formed on the device
 
 Julia's trailing ``!`` is spelled as a trailing underscore.  Arrays use the
 reference's column-major layouts (numpy ``order="F"``).
@@ -272,6 +274,65 @@ class DeviceProblem:
             self.h, None if pc is None else _vp(pc), 0 if pc is None else len(pc),
             None if uv_history is None else _vp(uv_history), _vp(out3)))
         return out3
+
+    # -- states and populations alone (qgd_eval_states / qgd_eval_populations) ---
+    def observables_supported(self):
+        """eval_states / eval_populations are single-GPU calls: not for a handle with a communicator or a partition."""
+        part = np.zeros(8, dtype=np.int32)
+        _lib.check(self.h, self.lib.qgd_get_partition(self.h, _vp(part)))
+        return part[6] == 1 and self.comm_info()["rank"] < 0
+
+    def _slots(self):
+        return 1 + self.nsteps // getattr(self, "_save_every", 1)
+
+    def _pcof_arg(self, pcof):
+        if pcof is not None and getattr(self, "_general", None):
+            self._upload_general(pcof)
+            pcof = None                                   # (the tables are on the device)
+        pc = None if pcof is None else np.ascontiguousarray(pcof, dtype=np.float64)
+        return pc, (None if pc is None else _vp(pc)), (0 if pc is None else len(pc))
+
+    def eval_states(self, pcof=None, forcing=None, out=None):
+        """The state trajectory alone, ``[2N, 1 + nsteps // save_every, n_cols]`` (Fortran order): Taylor index 0 of the
+        ``uv_history`` of eval_forward, bit for bit, without the stage derivatives being formed or moved.  ``forcing``: as
+        eval_forward_forced.  ``out``: an array to fill (e.g. a pinned one).  The scalars of the call are left in
+        ``self.last_scalars``."""
+        shape = (2 * self.N, self._slots(), self.c)
+        fo = None
+        if forcing is not None:
+            fo = np.asfortranarray(forcing, dtype=np.float64)
+            want = (2 * self.N, self.m, self.nsteps + 1, self.c)
+            if fo.shape != want:
+                raise ValueError(f"forcing must have shape {want}")
+        out = np.zeros(shape, order="F") if out is None else _check_out(out, shape, "out")
+        out3 = np.zeros(3)
+        pc, ptr, n = self._pcof_arg(pcof)
+        _lib.check(self.h, self.lib.qgd_eval_states(self.h, ptr, n, None if fo is None else _vp(fo), _vp(out), _vp(out3)))
+        self.last_scalars = out3
+        return out
+
+    def eval_populations(self, pcof=None, level_map=None, history_precomputed=False, out=None):
+        """Level populations along the sweep, formed on the device: ``[N, 1 + nsteps // save_every, n_cols]`` (what the
+        reference's get_populations makes of uv_history), or with ``level_map`` ``[n_groups, N]`` the contraction
+        ``level_map @ populations`` of every (time point, column), ``[n_groups, ..]`` (subsystem_population_map: per-qudit
+        level populations).  ``history_precomputed``: reuse the stored forward sweep when it belongs to this pcof."""
+        rows, lm = self.N, None
+        if level_map is not None:
+            lm = np.asarray(level_map)
+            if lm.ndim != 2 or lm.shape[1] != self.N or lm.shape[0] < 1 or not np.issubdtype(lm.dtype, np.number) \
+                    or np.iscomplexobj(lm):
+                raise ValueError(f"level_map must be a real [n_groups >= 1, {self.N}] array; got {lm.dtype} {lm.shape}")
+            lm = np.asfortranarray(lm, dtype=np.float64)
+            rows = lm.shape[0]
+        shape = (rows, self._slots(), self.c)
+        out = np.zeros(shape, order="F") if out is None else _check_out(out, shape, "out")
+        out3 = np.zeros(3)
+        pc, ptr, n = self._pcof_arg(pcof)
+        _lib.check(self.h, self.lib.qgd_eval_populations(self.h, ptr, n, 1 if history_precomputed else 0,
+                                                         None if lm is None else _vp(lm), rows if lm is not None else 0,
+                                                         _vp(out), _vp(out3)))
+        self.last_scalars = out3
+        return out
 
     def discrete_adjoint(self, pcof, history_precomputed=False, uv_history=None, lambda_history=None,
                          adjoint_forcing=None):
@@ -561,9 +622,62 @@ def eval_forward_(uv_history, prob, controls, pcof, order=2, saveEveryNsteps=1, 
 
 def eval_forward(prob, controls, pcof, order=2, saveEveryNsteps=1, forcing=None):
     """forward_evolution.jl:15-29: complex state history ``[N, 1+nsteps, N_initial_conditions]``."""
-    hist = np.zeros(_history_shape(prob, order, int(saveEveryNsteps)), order="F")
-    eval_forward_(hist, prob, controls, pcof, order=order, saveEveryNsteps=saveEveryNsteps, forcing=forcing)
-    return real_to_complex(hist[:, 0, :, :])
+    dp = device_problem(prob, order) if int(saveEveryNsteps) >= 1 else None
+    if dp is None or not dp.observables_supported():
+        hist = np.zeros(_history_shape(prob, order, int(saveEveryNsteps)), order="F")
+        eval_forward_(hist, prob, controls, pcof, order=order, saveEveryNsteps=saveEveryNsteps, forcing=forcing)
+        return real_to_complex(hist[:, 0, :, :])
+    # the states are all that is returned: they alone are laid out and downloaded (qgd_eval_states), the same bits
+    dp.set_controls(controls)
+    dp.set_save_every(int(saveEveryNsteps))
+    try:
+        return real_to_complex(dp.eval_states(pcof, forcing=forcing))
+    finally:
+        dp.set_save_every(1)
+
+
+def get_populations(history):
+    """get_populations (state_vector_helpers.jl:10-52): level populations ``u^2 + v^2`` of a real history array
+    ``[2N, 1+m, nt]`` or ``[2N, 1+m, nt, n_cols]`` -> ``[N, nt]`` / ``[N, nt, n_cols]``; the derivative axis is dropped.
+    Host arithmetic on an array that is already there; eval_populations forms the same on the device."""
+    h = np.asarray(history)
+    if h.ndim not in (3, 4) or not np.issubdtype(h.dtype, np.floating) or h.shape[0] % 2:
+        raise ValueError("history must be a real array [2N, 1+m, nt] or [2N, 1+m, nt, n_cols]")
+    N = h.shape[0] // 2
+    return np.asfortranarray(h[:N, 0] ** 2 + h[N:, 0] ** 2)
+
+
+def subsystem_population_map(subsystem_sizes):
+    """The 0/1 map ``[sum(sizes), prod(sizes)]`` of per-subsystem level populations for eval_populations: row
+    ``sum(sizes[:q]) + l`` adds up the levels of the full system whose subsystem q is in level l.  Digit order of
+    lowering_operators_system / basis_state: the first subsystem is the slowest digit of the level index."""
+    sizes = [int(s) for s in subsystem_sizes]
+    if not sizes or any(s < 1 for s in sizes):
+        raise ValueError("subsystem_sizes must be positive integers")
+    N = int(np.prod(sizes))
+    M = np.zeros((sum(sizes), N), order="F")
+    idx, row, stride = np.arange(N), 0, N
+    for s in sizes:
+        stride //= s
+        M[row + (idx // stride) % s, idx] = 1.0
+        row += s
+    return M
+
+
+def eval_populations(prob, controls, pcof, order=2, saveEveryNsteps=1, level_map=None):
+    """Level populations along the forward sweep, ``[N, 1 + nsteps // saveEveryNsteps, N_initial_conditions]`` -- what
+    ``get_populations`` makes of the history of eval_forward_ -- or, with ``level_map`` ``[n_groups, N]``, their contraction
+    ``[n_groups, ..]``, formed on the device: neither the stage derivatives nor the states leave it."""
+    save = int(saveEveryNsteps)
+    if save < 1:
+        raise ValueError("saveEveryNsteps must be a positive integer")
+    dp = device_problem(prob, order)
+    dp.set_controls(controls)
+    dp.set_save_every(save)
+    try:
+        return dp.eval_populations(pcof, level_map=level_map)
+    finally:
+        dp.set_save_every(1)
 
 
 def eval_grad_forced(prob, controls, pcof, target, order=2, cost_type="Infidelity"):
