@@ -1,8 +1,9 @@
-// qgd_host.h -- what the four host-side translation units of the C ABI share (include/qgd.h): the handle, the error and
+// qgd_host.h -- what the five host-side translation units of the C ABI share (include/qgd.h): the handle, the error and
 // launch macros, the phase timer and the internal entry points of each unit.
 //   qgd_host_alloc.cpp    handles: creation, validation (SchrodingerProb.jl:73-154), the time grid and its windows, setters
 //   qgd_host_eval.cpp     one evaluation: forward / adjoint phases, result transport, the evaluation entry points
-//   qgd_host_windows.cpp  time grids in bounded memory: window entry, the windowed forward and adjoint passes, their outputs
+//   qgd_host_output.cpp   reference-layout output arrays of a resident or windowed grid: the copy stream, staging, the one transport
+//   qgd_host_windows.cpp  time grids in bounded memory: window entry, the windowed forward and adjoint passes
 //   qgd_host_comm.cpp     several GPUs: the RCCL binding, the collective evaluation and its failure mode
 // There is no CPU fallback: without a GPU every compute entry point fails.
 #pragma once
@@ -365,16 +366,16 @@ void drop_graph(qgd_handle h);
 int plan_windows(qgd_handle h, int chunks, int win);
 int alloc_grid(qgd_handle h);
 
-// qgd_host_eval.cpp
+// qgd_host_output.cpp
 qgd_handle_s::HostReg *find_reg(qgd_handle h, const void *p, size_t bytes);
-int copy_side(qgd_handle h);
-int hand_over(qgd_handle h);
 int finish_copies(qgd_handle h);
-int download(qgd_handle h, void *dst, const void *src, size_t row_bytes, size_t rows);
-int copy_history_out(qgd_handle h, double *uv_history, int save = 1);
-int copy_panels_out(qgd_handle h, const double *panels, double **stage, double *out, size_t J, int n_first);
-int copy_lambda_full_out(qgd_handle h, double *out);
+int grow_stage(qgd_handle h, double **p, size_t *len, size_t need);
+int history_out(qgd_handle h, double *uv_history, int save = 1);
+int panels_out(qgd_handle h, const double *panels, double **stage, double *out, size_t J, int n_first);
+int lambda_history_out(qgd_handle h, double *out);
 int observe_out(qgd_handle h, const Observe &obs, int save);
+
+// qgd_host_eval.cpp
 int upload_pcof(qgd_handle h, const double *pcof, int n_pcof);
 int forward_begin(qgd_handle h, const double *pcof, int n_pcof, bool allow_front = false);
 int forward_end(qgd_handle h);
@@ -382,9 +383,6 @@ int adjoint_begin(qgd_handle h);
 int adjoint_end(qgd_handle h);
 
 // qgd_host_windows.cpp
-int window_history_out(qgd_handle h, double *uv_history, int save = 1);
-int window_lambda_full_out(qgd_handle h, double *out);
-int window_panels_out(qgd_handle h, const double *panels, double **stage, double *out, size_t J, int n_first);
 int enter_window(qgd_handle h, const double *pcof, int r, bool with_start_state);
 int chunk_forward(qgd_handle h, const double *pcof, int n_pcof, int r, bool rerun);
 int chunked_forward(qgd_handle h, const double *pcof, int n_pcof, double *uv_history = nullptr, int save = 1, const Observe *obs = nullptr);

@@ -206,10 +206,10 @@ int comm_discrete_adjoint_body(qgd_handle h, const double *pcof, int n_pcof, int
         if (!time && (rc = comm_collective(h, 3))) return rc;      // <w_N,R>, <w_N,T>, guard: global before the terminal condition
     }
     if (!time) { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal_given(&k)); }
-    if (adjoint_forcing && (rc = copy_panels_out(h, k.forcing, &h->stage_f, adjoint_forcing, 1, 0))) return rc;
+    if (adjoint_forcing && (rc = panels_out(h, k.forcing, &h->stage_f, adjoint_forcing, 1, 0))) return rc;
     if (uv_history) {
         if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
-        if ((rc = copy_history_out(h, uv_history))) return rc;
+        if ((rc = history_out(h, uv_history))) return rc;
     }
     if ((rc = adjoint_begin(h))) return rc;
     if (time && (rc = comm_collective(h, 1))) return rc;
@@ -243,7 +243,7 @@ int comm_eval_forward_body(qgd_handle h, const double *pcof, int n_pcof, double 
     if (uv_history) {
         { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
         h->sweep.derivs = true;
-        if ((rc = copy_history_out(h, uv_history, h->save_every))) return rc;
+        if ((rc = history_out(h, uv_history, h->save_every))) return rc;
     }
     K_TRY(h, qgdk_flag_to_scal(&k));      // a singular step matrix on ANY rank fails the call on every rank
     if ((rc = comm_collective(h, 3))) { (void)finish_copies(h); return rc; }

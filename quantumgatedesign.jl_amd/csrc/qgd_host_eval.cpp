@@ -1,203 +1,8 @@
 // qgd_host_eval.cpp -- host side of the C ABI (include/qgd.h), one evaluation: the forward and adjoint phases (orchestration mirrors eval_forward!, src/forward_evolution.jl:33-70, and
-// discrete_adjoint!, src/eval_grad_discrete_adjoint.jl:107-160), the transport of results and output arrays, the evaluation entry points.
+// discrete_adjoint!, src/eval_grad_discrete_adjoint.jl:107-160), the transport of results, the evaluation entry points.
 #include "qgd_host.h"
 
 namespace qgdh {
-
-
-qgd_handle_s::HostReg *find_reg(qgd_handle h, const void *p, size_t bytes)
-{
-    for (auto &r : h->regs)
-        if ((const char *)p >= (const char *)r.host && (const char *)p + bytes <= (const char *)r.host + r.bytes) return &r;
-    return nullptr;
-}
-
-
-int copy_side(qgd_handle h)
-{
-    if (!h->copy_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    // (two DMA engines for a large pinned download: 1.24 -> 0.87 ms for the reference-shaped cnot3 call on a box whose single
-    //  engine path was slow)
-    if (!h->copy_stream2) HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream2, hipStreamNonBlocking));
-    if (!h->ev_ready) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_ready, hipEventDisableTiming));
-    return QGD_OK;
-}
-
-
-// the copy stream takes over from the compute stream at this point of the launch sequence
-int hand_over(qgd_handle h)
-{
-    HIP_TRY(h, hipEventRecord(h->ev_ready, h->k.stream));
-    HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->ev_ready, 0));
-    if (h->copy_stream2) HIP_TRY(h, hipStreamWaitEvent(h->copy_stream2, h->ev_ready, 0));
-    h->copies_pending = true;
-    return QGD_OK;
-}
-
-
-int finish_copies(qgd_handle h)
-{
-    if (h->copies_pending) {
-        // (spinning on hipStreamQuery, or on an event recorded behind the copies: no difference, 0.94 ms either way)
-        HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
-        if (h->copy_stream2) HIP_TRY(h, hipStreamSynchronize(h->copy_stream2));
-        h->copies_pending = false;
-    }
-    return QGD_OK;
-}
-
-
-// Device-to-host download on the copy stream.  A plain hipMemcpyAsync into REGISTERED host memory runs as a blit kernel
-// (__amd_rocclr_copyBuffer): its waves fill the CUs and starve the adjoint chain kernels beside it (15 -> 410 us for the
-// first of them on cnot3), which delays lambda and leaves the PCIe link idle at the end of the evaluation.  The same
-// bytes as a pitched (rows x row_bytes, pitch = row_bytes) copy go through the DMA engine and leave the CUs alone.
-int download(qgd_handle h, void *dst, const void *src, size_t row_bytes, size_t rows)
-{
-    if (rows <= 1 || !find_reg(h, dst, row_bytes * rows))
-        HIP_TRY(h, hipMemcpyAsync(dst, src, row_bytes * rows, hipMemcpyDeviceToHost, h->copy_stream));
-    else if (h->copy_stream2 && rows >= 2 && row_bytes * rows > ((size_t)8 << 20)) {      // (experiment: two DMA engines side by side)
-        const size_t r1 = rows / 2;
-        HIP_TRY(h, hipMemcpy2DAsync(dst, row_bytes, src, row_bytes, row_bytes, r1, hipMemcpyDeviceToHost, h->copy_stream));
-        HIP_TRY(h, hipMemcpy2DAsync((char *)dst + r1 * row_bytes, row_bytes, (const char *)src + r1 * row_bytes, row_bytes, row_bytes, rows - r1,
-                                    hipMemcpyDeviceToHost, h->copy_stream2));
-    } else
-        HIP_TRY(h, hipMemcpy2DAsync(dst, row_bytes, src, row_bytes, row_bytes, rows, hipMemcpyDeviceToHost, h->copy_stream));
-    return QGD_OK;
-}
-
-
-// state history: panels hist [nt][Np][2cp] (j = 0) and dpsi [nt][m][Np][2cp] (j = 1..m) -> the reference's
-// uv_history[2N, 1+m, nt, c] (forward_evolution.jl:42-44).  Asynchronous: finish_copies() before returning.
-// (Writing registered host arrays in place with a few persistent workgroups instead of staging + copying was measured slower
-// in round 2 -- 0.96 ms at best against 0.91 for the 31.6 MB of the cnot3 call -- and is gone.)
-int copy_history_out(qgd_handle h, double *uv_history, int save)
-{
-    qgdk_ctx &k = h->k;
-    // save > 1 (eval_forward's saveEveryNsteps, forward_evolution.jl:104,178,239-241): slot s of the output holds time
-    // point s * save -- the re-layout kernel reads the panels with a stride of `save` time points
-    const size_t hstep = (size_t)k.Np * 2 * k.cp * (size_t)save, nt = 1 + ((size_t)k.nt - 1) / (size_t)save, m = k.m, n2 = 2 * (size_t)k.N;
-    int rc = copy_side(h);
-    if (rc) return rc;
-    const long long dcol = (long long)(nt * (m + 1) * n2), dn = (long long)((m + 1) * n2), dj = (long long)n2;
-    // (the staging buffer is sized for the full grid: a strided call uses its front)
-    if (!h->stage_hist && (rc = dev_alloc(h, h->stage_bufs, &h->stage_hist, n2 * (m + 1) * (size_t)k.nt * k.c))) return rc;
-    K_TRY(h, qgdk_layout(&k, k.hist, (long long)hstep, 0, h->stage_hist, dcol, dn, dj, 0, (int)nt, 1, 0, k.stream, 0));
-    K_TRY(h, qgdk_layout(&k, k.dpsi, (long long)(m * hstep), (long long)(hstep / save), h->stage_hist + n2, dcol, dn, dj, 0, (int)nt, (int)m, 0, k.stream, 0));
-    if ((rc = hand_over(h))) return rc;
-    return download(h, uv_history, h->stage_hist, n2 * (m + 1) * sizeof(double), nt * k.c);
-}
-
-
-// one panel per time point (lambda, adjoint forcing) -> [2N, J, nt, c] with only Taylor index 0 written
-// (J = 1: adjoint_forcing; J = 1+m: lambda_history, whose other columns are zero)
-int copy_panels_out(qgd_handle h, const double *panels, double **stage, double *out, size_t J, int n_first)
-{
-    qgdk_ctx &k = h->k;
-    const size_t hstep = (size_t)k.Np * 2 * k.cp, nt = k.nt, n2 = 2 * (size_t)k.N;
-    const size_t compact = n2 * nt * k.c;
-    int rc = copy_side(h);
-    if (rc) return rc;
-    qgd_handle_s::HostReg *reg = find_reg(h, out, compact * J * sizeof(double));
-    if (!*stage) {
-        if ((rc = dev_alloc(h, h->stage_bufs, stage, compact))) return rc;
-        HIP_TRY(h, hipMemsetAsync(*stage, 0, compact * sizeof(double), k.stream));     // time points below n_first stay zero
-    }
-    K_TRY(h, qgdk_layout(&k, panels, (long long)hstep, 0, *stage, (long long)(nt * n2), (long long)n2, 0, n_first, (int)nt - n_first, 1, 0, k.stream, 0));
-    if ((rc = hand_over(h))) return rc;
-    if (J == 1) {
-        return download(h, out, *stage, n2 * sizeof(double), nt * k.c);
-    }
-    if (reg) {      // pinned destination: strided copy of the j = 0 columns; the rest is zero-filled once
-        if (!reg->zeroed) { memset(out, 0, compact * J * sizeof(double)); reg->zeroed = true; }
-        HIP_TRY(h, hipMemcpy2DAsync(out, J * n2 * sizeof(double), *stage, n2 * sizeof(double), n2 * sizeof(double), nt * k.c,
-                                    hipMemcpyDeviceToHost, h->copy_stream));
-        return QGD_OK;
-    }
-    h->scatter_tmp.resize(compact);
-    HIP_TRY(h, hipMemcpyAsync(h->scatter_tmp.data(), *stage, compact * sizeof(double), hipMemcpyDeviceToHost, h->copy_stream));
-    HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
-    memset(out, 0, compact * J * sizeof(double));
-    for (size_t r = 0; r < nt * (size_t)k.c; r++) memcpy(out + r * J * n2, h->scatter_tmp.data() + r * n2, n2 * sizeof(double));
-    return QGD_OK;
-}
-
-
-// lambda_history with its derivative columns (qgd_set_lambda_derivatives): lam [nt][Np][2cp] (j = 0) and
-// dlam [nt][m][Np][2cp] (k_adjoint_derivs, j = 1..m) -> [2N, 1+m, nt, c] for time indices 1 .. nt-1; index 0 stays
-// zero, as in the reference (forward_evolution.jl:414-480).  Asynchronous: finish_copies() before returning.
-int copy_lambda_full_out(qgd_handle h, double *out)
-{
-    qgdk_ctx &k = h->k;
-    const size_t hstep = (size_t)k.Np * 2 * k.cp, nt = k.nt, m = k.m, n2 = 2 * (size_t)k.N;
-    const size_t total = n2 * (m + 1) * nt * k.c;
-    int rc = copy_side(h);
-    if (rc) return rc;
-    if (!h->dlam) {
-        if ((rc = dev_alloc(h, h->stage_bufs, &h->dlam, nt * std::max<size_t>(m, 1) * hstep))) return rc;
-        if ((m + 1) * (size_t)k.Np * 16 * sizeof(double) > 150 * 1024 &&
-            (rc = dev_alloc(h, h->stage_bufs, &h->dlam_scratch, (nt - 1) * (size_t)(k.cp / 8) * (m + 1) * k.Np * 16))) return rc;
-        if ((rc = dev_alloc(h, h->stage_bufs, &h->stage_lam_full, total))) return rc;
-        HIP_TRY(h, hipMemsetAsync(h->stage_lam_full, 0, total * sizeof(double), k.stream));
-    }
-    { PhaseTimer t(h, "lambda_derivs"); K_TRY(h, qgdk_adjoint_derivs(&k, h->dlam, h->dlam_scratch)); }
-    const long long dcol = (long long)(nt * (m + 1) * n2), dn = (long long)((m + 1) * n2), dj = (long long)n2;
-    K_TRY(h, qgdk_layout(&k, k.lam, (long long)hstep, 0, h->stage_lam_full, dcol, dn, dj, 1, (int)nt - 1, 1, 0, k.stream, 0));
-    K_TRY(h, qgdk_layout(&k, h->dlam, (long long)(m * hstep), (long long)hstep, h->stage_lam_full + n2, dcol, dn, dj, 1, (int)nt - 1, (int)m, 0, k.stream, 0));
-    if ((rc = hand_over(h))) return rc;
-    return download(h, out, h->stage_lam_full, n2 * (m + 1) * sizeof(double), nt * k.c);
-}
-
-
-// a staging buffer of stage_bufs that grows to the largest request (the copies that read the old one were awaited by the
-// call that issued them)
-static int grow_stage(qgd_handle h, double **p, size_t *len, size_t need)
-{
-    if (*p && *len >= need) return QGD_OK;
-    if (*p) {
-        auto it = std::find(h->stage_bufs.begin(), h->stage_bufs.end(), (void *)*p);
-        if (it != h->stage_bufs.end()) h->stage_bufs.erase(it);
-        (void)hipFree(*p);
-        *p = nullptr; *len = 0;
-    }
-    int rc = dev_alloc(h, h->stage_bufs, p, need);
-    if (!rc) *len = need;
-    return rc;
-}
-
-
-// qgd_eval_states / qgd_eval_populations: the state panels hist [nt][Np][2cp] of the grid -- or of the window of a windowed
-// grid that is in the buffers -- -> the caller's [rows, 1 + (nt_glob-1)/save, c] at the window's slots, rows = 2N (the states:
-// Taylor index 0 of uv_history, through the same re-layout kernel), N (level populations) or n_groups (populations contracted
-// with the level map in obs_map).  No stage derivatives, a staging buffer of exactly the bytes that leave.  Resident grid:
-// asynchronous like copy_history_out (finish_copies() before returning); a window's copy is awaited here, like
-// window_history_out's, before the next window overwrites the panels.
-int observe_out(qgd_handle h, const Observe &obs, int save)
-{
-    qgdk_ctx &k = h->k;
-    const size_t hstep = (size_t)k.Np * 2 * k.cp, ntg = (size_t)k.nt_glob, sv = (size_t)save;
-    const size_t rows = obs.kind == OBS_STATES ? 2 * (size_t)k.N : (obs.n_groups > 0 ? (size_t)obs.n_groups : (size_t)k.N);
-    // slot s of the output holds GLOBAL time point s * save; the buffers hold the points n_off .. n_off + nt - 1
-    const size_t g_lo = (size_t)k.n_off, g_hi = (size_t)k.n_off + (size_t)k.nt - 1;
-    const size_t s_lo = (g_lo + sv - 1) / sv, s_hi = g_hi / sv;
-    if (s_hi < s_lo) return QGD_OK;                                                  // (no saved point falls into this window)
-    const size_t cnt = s_hi - s_lo + 1, loc = s_lo * sv - g_lo, slots = 1 + (ntg - 1) / sv;
-    int rc = copy_side(h);
-    if (rc) return rc;
-    if ((rc = grow_stage(h, &h->stage_obs, &h->stage_obs_len, rows * cnt * k.c))) return rc;
-    const double *src = k.hist + loc * hstep;
-    if (obs.kind == OBS_STATES) {
-        K_TRY(h, qgdk_layout(&k, src, (long long)(hstep * sv), 0, h->stage_obs, (long long)(cnt * rows), (long long)rows, 0, 0, (int)cnt, 1, 0, k.stream, 0));
-    } else {
-        PhaseTimer t(h, "populations");
-        K_TRY(h, qgdk_populations(&k, src, (long long)(hstep * sv), h->stage_obs, (long long)(cnt * rows), (long long)rows, (int)cnt,
-                                  obs.n_groups > 0 ? h->obs_map : nullptr, obs.n_groups, k.stream));
-    }
-    if ((rc = hand_over(h))) return rc;
-    if (h->chunks_eff == 1) return download(h, obs.out, h->stage_obs, rows * sizeof(double), cnt * k.c);      // (cnt == slots)
-    const size_t row = cnt * rows * sizeof(double);
-    HIP_TRY(h, hipMemcpy2DAsync(obs.out + s_lo * rows, slots * rows * sizeof(double), h->stage_obs, row, row, (size_t)k.c, hipMemcpyDeviceToHost, h->copy_stream));
-    return finish_copies(h);
-}
 
 
 int upload_pcof(qgd_handle h, const double *pcof, int n_pcof)
@@ -325,7 +130,7 @@ int adjoint_end(qgd_handle h)
     if (!k.front) { PhaseTimer t(h, "lambda"); K_TRY(h, qgdk_lambda(&k)); }      // (fused front: the sweep ran in lambda itself)
     if (h->lambda_out) {      // its download runs beside the gradient kernels
         double *out = h->lambda_out; h->lambda_out = nullptr;
-        int rc = h->lambda_derivs ? copy_lambda_full_out(h, out) : copy_panels_out(h, k.lam, &h->stage_lam, out, (size_t)k.m + 1, 1);
+        int rc = lambda_history_out(h, out);
         if (rc) return rc;
     }
     if (!h->sweep.derivs && qgdk_gradient_needs_derivs(&k)) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
@@ -477,7 +282,7 @@ int qgd_eval_forward(qgd_handle h, const double *pcof, int32_t n_pcof, double *u
         { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
         h->sweep.derivs = true;
     }
-    if (uv_history && (rc = copy_history_out(h, uv_history, h->save_every))) return rc;
+    if (uv_history && (rc = history_out(h, uv_history, h->save_every))) return rc;
     if ((rc = fetch_results(h, nullptr, out3))) { (void)finish_copies(h); return rc; }
     return finish_copies(h);
 }
@@ -564,10 +369,10 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, int32
     // The downloads run on the copy stream beside the adjoint sweep and are what bounds this form of the call (PCIe):
     // the guard forcing goes first -- it is final once the forward sweep is (eval_grad_discrete_adjoint.jl:732-752) and
     // keeps the link busy while the stage derivatives of the state history are still being computed and laid out
-    if (adjoint_forcing && (rc = copy_panels_out(h, k.forcing, &h->stage_f, adjoint_forcing, 1, 0))) return rc;
+    if (adjoint_forcing && (rc = panels_out(h, k.forcing, &h->stage_f, adjoint_forcing, 1, 0))) return rc;
     if (uv_history) {
         if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
-        if ((rc = copy_history_out(h, uv_history))) return rc;
+        if ((rc = history_out(h, uv_history))) return rc;
     }
     if ((rc = adjoint_begin(h))) return rc;
     h->lambda_out = lambda_history;
@@ -631,7 +436,7 @@ static int forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, cons
         if (uv_history) {
             { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
             K_TRY(h, qgdk_forcing_add_derivs(&k));     // w_j = D_j w_0 + E_j
-            if ((rc = W > 1 ? window_history_out(h, uv_history, h->save_every) : copy_history_out(h, uv_history, h->save_every))) return rc;
+            if ((rc = history_out(h, uv_history, h->save_every))) return rc;
         }
         if (states && (rc = observe_out(h, Observe{OBS_STATES, 0, states}, h->save_every))) return rc;
     }
@@ -867,10 +672,9 @@ int qgd_eval_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, const dou
         if (r == W - 1)      // lambda_N is the given one (not L_N^-H L_N^H of it)
             HIP_TRY(h, hipMemcpyAsync(k.lam + (nt - 1) * hstep, lamN.data(), hstep * sizeof(double), hipMemcpyHostToDevice, k.stream));
         // (with qgd_set_lambda_derivatives the reference's derivative columns too, forward_evolution.jl:427-433, :471-480)
-        // (a resident grid takes copy_panels_out, which zero-fills the staging buffer it allocates: time index 0 stays zero)
-        if (W > 1) rc = h->lambda_derivs ? window_lambda_full_out(h, lambda_history) : window_panels_out(h, k.lam, &h->stage_lam, lambda_history, m + 1, 1);
-        else rc = h->lambda_derivs ? copy_lambda_full_out(h, lambda_history) : copy_panels_out(h, k.lam, &h->stage_lam, lambda_history, m + 1, 1);
-        const int rc2 = finish_copies(h);      // (copy_*_out leave their download running)
+        // (a resident grid downloads its zero-filled staging buffer whole: time index 0 stays zero)
+        rc = lambda_history_out(h, lambda_history);
+        const int rc2 = finish_copies(h);      // (a resident grid's download is left running)
         if (rc || rc2) return rc ? rc : rc2;
         if (r > 0) HIP_TRY(h, hipMemcpyAsync(h->carry_y, k.yhist, hstep * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
     }

@@ -153,6 +153,52 @@ def test_chunked_grid_matches_resident(qgd, which, order, nsteps, windows):
     dp.close()
 
 
+def test_windowed_grid_into_registered_arrays(qgd):
+    """The reference-shaped call on a windowed grid whose three output arrays are registered (qgd_register_host_buffer): every
+    window's pitched copies land in pinned memory at the window's slots.  Equal to a resident handle's pageable arrays, with the
+    derivative columns of lambda_history switched on and off again between calls; time index 0 of lambda_history and, without
+    the derivatives, its columns 1..m are exactly zero.  (The arrays asked for keep the call off the small-problem path.)"""
+    order, nsteps = 4, 24
+    prob, ctrl, pcof, target = cases.cnot2_case(qgd, nsteps=nsteps, tf=float(nsteps))
+    shape = (prob.real_system_size, 1 + order // 2, 1 + nsteps, prob.N_initial_conditions)
+    new = lambda fill: [np.full(shape, fill, order="F"), np.full(shape, fill, order="F"), np.full((shape[0], shape[2], shape[3]), fill, order="F")]
+    chk = qgd.DeviceProblem(prob, order); chk.set_controls(ctrl); chk.set_target(target)
+    assert chk.memory_plan()["windows"] == 1
+    full = chk.memory_plan()["window_bytes"]
+    refs = {}
+    for derivs in (False, True):
+        chk.set_lambda_derivatives(derivs)
+        refs[derivs] = new(0.0)
+        chk.discrete_adjoint(pcof, False, *refs[derivs])
+    chk.close()
+    assert np.abs(refs[True][1][:, 1:, 1:]).max() > 0 and not refs[False][1][:, 1:].any()
+    dp = qgd.DeviceProblem(prob, order)
+    dp.set_memory_budget(int(full / 3 * 1.15))
+    dp.set_controls(ctrl); dp.set_target(target)
+    plan = dp.memory_plan()
+    assert plan["windows"] >= 3, plan
+    got = new(np.nan)
+    for a in got:
+        dp.pin(a)
+    for call, derivs in enumerate((False, True, False)):
+        dp.set_lambda_derivatives(derivs)
+        if call:      # (lambda_history keeps the derivative columns of the call before: the last call must clear them)
+            got[0][...] = np.nan; got[2][...] = np.nan
+        dp.discrete_adjoint(pcof, False, *got)
+        for name, a, b in zip(("uv_history", "lambda_history", "adjoint_forcing"), got, refs[derivs]):
+            for j in range(a.shape[1] if a.ndim == 4 else 1):      # per Taylor index
+                x, y = (a[:, j], b[:, j]) if a.ndim == 4 else (a, b)
+                err = np.abs(x - y).max()
+                print(f"call {call} derivs {derivs} {name}[{j}]: max abs err {err:.3e}, scale {max(1.0, np.abs(y).max()):.3e}")
+                assert np.isfinite(x).all() and err <= 1e-11 * max(1.0, np.abs(y).max()), (call, name, j)
+        assert not got[1][:, :, 0].any(), call                       # time index 0 is never written
+        if not derivs:
+            assert not got[1][:, 1:].any(), call                     # (exactly zero, again after the call that filled them)
+        else:
+            assert np.abs(got[1][:, 1:, 1:]).max() > 0
+    dp.close()      # (unpins)
+
+
 def test_budget_too_small_is_a_memory_error(qgd):
     prob, ctrl, pcof, target = cases.cnot3_case(qgd, nsteps=40, tf=40.0)
     dp = qgd.DeviceProblem(prob, 8)
