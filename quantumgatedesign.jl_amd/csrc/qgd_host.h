@@ -1,7 +1,8 @@
-// qgd_host.h -- what the five host-side translation units of the C ABI share (include/qgd.h): the handle, the error and
+// qgd_host.h -- what the six host-side translation units of the C ABI share (include/qgd.h): the handle, the error and
 // launch macros, the phase timer and the internal entry points of each unit.
 //   qgd_host_alloc.cpp    handles: creation, validation (SchrodingerProb.jl:73-154), the time grid and its windows, setters
 //   qgd_host_eval.cpp     one evaluation: forward / adjoint phases, result transport, the evaluation entry points
+//   qgd_host_sens.cpp     sensitivities of the state to the parameters: the forced gradient, the exact Hessian, Hessian-vector products
 //   qgd_host_output.cpp   reference-layout output arrays of a resident or windowed grid: the copy stream, staging, the one transport
 //   qgd_host_windows.cpp  time grids in bounded memory: window entry, the windowed forward and adjoint passes
 //   qgd_host_comm.cpp     several GPUs: the RCCL binding, the collective evaluation and its failure mode
@@ -13,7 +14,6 @@
 #include <sys/mman.h>
 #include <sys/syscall.h>
 #include <unistd.h>
-#include <cctype>
 #include <sched.h>
 
 #include <cctype>
@@ -83,9 +83,10 @@ struct qgd_handle_s {
     std::vector<void *> static_bufs, grid_bufs, basis_bufs, forced_bufs;
     std::vector<double> target_host;   // stacked real target [2N x c] (forced gradient: the overlaps are host arithmetic)
     size_t forced_key = 0;             // (nt, n_pcof) the forced-gradient buffers were sized for
+    double *fsc_forced = nullptr;      // (in forced_bufs) HBM work-panel slab of k_forced_basis when its panels exceed the LDS (N > 64)
     std::vector<void *> hess_bufs;     // qgd_eval_hessian: sensitivity history and the work buffers of qgd_k_hessian.hip
     size_t hess_key = 0;               // (nt, n_pcof, basis directions, general guard) they were sized for
-    double *hs_shist = nullptr, *hs_ws = nullptr, *hs_Z = nullptr, *hs_half = nullptr, *hs_slab = nullptr, *hs_zt = nullptr, *hs_Y = nullptr;
+    struct HessBufs { double *shist = nullptr, *ws = nullptr, *Z = nullptr, *half = nullptr, *slab = nullptr, *zt = nullptr, *Y = nullptr; } hs;
     // qgd_eval_hessian_vec: the direction-independent setup of a product -- forward sweep, lambda, stage
     // derivatives, the forced basis responses (in forced_bufs), Z and the halves of e_n -- stays on the handle.  hvp_valid: it
     // belongs to the stored sweep (StoredSweep::pcof) and the present target, cost type, basis and grid; every transition of
@@ -99,8 +100,8 @@ struct qgd_handle_s {
     size_t hvp_key = 0;                // (nt, n_pcof, basis directions, general guard, scan blocks) they were sized for
     bool hvp_valid = false;
     std::vector<double> hvp_grad;      // the adjoint gradient of the setup
-    double *fsc_forced = nullptr, *fsc_forcing = nullptr;   // HBM work-panel slabs of the forced kernels when they exceed the LDS (N > 64)
     std::vector<void *> forcing_bufs;  // eval_forward with a user forcing
+    double *fsc_forcing = nullptr;     // (in forcing_bufs) the same slab for k_forcing_terms
     size_t forcing_key = 0;
     bool have_basis = false, have_tables = false;
     StoredSweep sweep;
@@ -360,8 +361,16 @@ RcclApi &rccl();
 enum ObserveKind { OBS_STATES, OBS_POPULATIONS };
 struct Observe { ObserveKind kind; int n_groups; double *out; };
 
+// A buffer plan: the device buffers of a keyed pool, each listed once -- where its pointer goes, its length in doubles, whether
+// this problem has it (else the pointer is set to NULL).  plan_bytes: what the plan asks for (without dev_alloc's pad);
+// plan_alloc: the pool anew from the plan, freed again when an allocation fails.
+struct Buf { double **slot; size_t count; bool on = true; };
+inline size_t plan_bytes(const std::vector<Buf> &plan) { size_t n = 0; for (const Buf &b : plan) n += b.on ? b.count : 0; return n * sizeof(double); }
+
 // qgd_host_alloc.cpp
 void free_pool(std::vector<void *> &pool);
+int plan_alloc(qgd_handle h, std::vector<void *> &pool, const std::vector<Buf> &plan);
+void free_sensitivity_buffers(qgd_handle h);
 void drop_graph(qgd_handle h);
 int plan_windows(qgd_handle h, int chunks, int win);
 int alloc_grid(qgd_handle h);
@@ -381,6 +390,11 @@ int forward_begin(qgd_handle h, const double *pcof, int n_pcof, bool allow_front
 int forward_end(qgd_handle h);
 int adjoint_begin(qgd_handle h);
 int adjoint_end(qgd_handle h);
+int run_forward(qgd_handle h, const double *pcof, int n_pcof, bool allow_front = false);
+bool tiny_applies(qgd_handle h, const double *pcof, int n_pcof);
+int tiny_evaluate(qgd_handle h, const double *pcof, int n_pcof, bool gradient, double *grad, double *out3);
+int check_status(qgd_handle h);
+int fetch_results(qgd_handle h, double *grad, double *out3, const double *src = nullptr);
 
 // qgd_host_windows.cpp
 int enter_window(qgd_handle h, const double *pcof, int r, bool with_start_state);
@@ -389,13 +403,6 @@ int chunked_forward(qgd_handle h, const double *pcof, int n_pcof, double *uv_his
 int chunked_adjoint(qgd_handle h, double *lambda_history = nullptr, double *adjoint_forcing = nullptr);
 int forcing_buffers(qgd_handle h, size_t nt, size_t B);
 int upload_forcing(qgd_handle h, const double *forcing, size_t nt, size_t n_off);
-
-// qgd_host_eval.cpp
-int run_forward(qgd_handle h, const double *pcof, int n_pcof, bool allow_front = false);
-bool tiny_applies(qgd_handle h, const double *pcof, int n_pcof);
-int tiny_evaluate(qgd_handle h, const double *pcof, int n_pcof, bool gradient, double *grad, double *out3);
-int check_status(qgd_handle h);
-int fetch_results(qgd_handle h, double *grad, double *out3, const double *src = nullptr);
 
 // qgd_host_comm.cpp
 RcclApi load_rccl();

@@ -22,6 +22,26 @@ void free_pool(std::vector<void *> &pool)
 }
 
 
+int plan_alloc(qgd_handle h, std::vector<void *> &pool, const std::vector<Buf> &plan)
+{
+    free_pool(pool);
+    for (const Buf &b : plan) {
+        *b.slot = nullptr;
+        const int rc = b.on ? dev_alloc(h, pool, b.slot, b.count) : QGD_OK;
+        if (rc) { free_pool(pool); return rc; }
+    }
+    return QGD_OK;
+}
+
+
+// the buffers of the forced gradient, the Hessian and the Hessian-vector product follow the grid and the control basis
+void free_sensitivity_buffers(qgd_handle h)
+{
+    for (auto *pool : {&h->forced_bufs, &h->hess_bufs, &h->hvp_bufs}) free_pool(*pool);
+    h->forced_key = h->hess_key = h->hvp_key = 0; hvp_void(h);
+}
+
+
 void drop_graph(qgd_handle h)
 {
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
@@ -181,9 +201,7 @@ int alloc_grid(qgd_handle h)
     drop_graph(h);
     h->grid_ready = false;
     free_pool(h->grid_bufs);
-    free_pool(h->forced_bufs); h->forced_key = 0;
-    free_pool(h->hess_bufs); h->hess_key = 0;
-    free_pool(h->hvp_bufs); h->hvp_key = 0; hvp_void(h);
+    free_sensitivity_buffers(h);
     free_pool(h->forcing_bufs); h->forcing_key = 0;
     free_pool(h->stage_bufs); h->stage_hist = h->stage_lam = h->stage_f = nullptr;
     h->stage_obs = h->obs_map = nullptr; h->stage_obs_len = h->obs_map_len = 0;
@@ -585,9 +603,7 @@ int qgd_set_control_basis(qgd_handle h, const int32_t *n_coeff, const double *co
     NEED_GRID(h);
     qgdk_ctx &k = h->k;
     free_pool(h->basis_bufs);
-    free_pool(h->forced_bufs); h->forced_key = 0;
-    free_pool(h->hess_bufs); h->hess_key = 0;
-    free_pool(h->hvp_bufs); h->hvp_key = 0; hvp_void(h);
+    free_sensitivity_buffers(h);
     h->have_basis = false;
     sweep_void(h); h->sweep.has_pcof = false;
     k.scal = h->scal_static; k.grad = nullptr; k.redbuf = nullptr; if (h->status_static) k.status = h->status_static;

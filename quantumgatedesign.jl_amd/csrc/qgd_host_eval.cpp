@@ -509,119 +509,6 @@ int qgd_eval_populations(qgd_handle h, const double *pcof, int32_t n_pcof, int32
 }
 
 
-// buffers of the forced gradient for (up to) nt time points and B scan blocks.  With `bytes`: nothing is allocated, the bytes
-// a call without it would allocate are added to *bytes (0 when the buffers are there already).
-static int forced_buffers(qgd_handle h, size_t nt, size_t B, size_t *bytes = nullptr)
-{
-    qgdk_ctx &k = h->k;
-    const size_t hstep = (size_t)k.Np * 2 * k.cp, NB = (size_t)k.n_ops * 2 * k.m;
-    const size_t cpS = (size_t)k.n_pcof * k.cp, hstepS = (size_t)k.Np * 2 * cpS;
-    const size_t key = (nt * 1000003u + (size_t)k.n_pcof) * 4099u + B;
-    if (h->forced_key != key) {
-        int rc = QGD_OK;
-        auto A = [&](double **p, size_t count) -> bool {
-            if (bytes) { *bytes += count * sizeof(double); return true; }
-            return (rc = dev_alloc(h, h->forced_bufs, p, count)) == QGD_OK;
-        };
-        if (!bytes) { free_pool(h->forced_bufs); h->forced_key = 0; h->fsc_forced = nullptr; }
-        if (!A(&k.fs_BR, nt * NB * hstep) || !A(&k.fs_BL, nt * NB * hstep) || !A(&k.fs_phi, B * hstepS) ||
-            !A(&k.fs_bnd, (B + 1) * hstepS) || !A(&k.fs_gacc, (size_t)k.n_pcof + 1)) return rc;
-        // (the 2m+2 work panels of k_forced_basis: LDS up to 150 KB, else an HBM slab per workgroup)
-        if (qgdk_forced_lds(k.Np, k.m) > 150 * 1024 && !A(&h->fsc_forced, nt * (size_t)(k.cp / 8) * (size_t)(2 * k.m + 2) * k.Np * 16)) return rc;
-        if (bytes) return QGD_OK;
-        h->forced_key = key;
-    }
-    if (!bytes) k.fs_scratch = h->fsc_forced;
-    return QGD_OK;
-}
-
-
-// The terminal part of the forced gradient from s_N, the sensitivities of the final state to every parameter (sN_dev: panels
-// with parameter p in columns p * cp ..), plus the guard part the forced sweeps accumulated in fs_gacc (grad may be NULL):
-//   :Infidelity  -(2/N_ess^2) (<w_N,R> <s_N,R> + <w_N,T> <s_N,T>), T = [R_im; -R_re] (infidelity.jl:13-17)
-//   :Tracking    d(0.5 |w_N - R|^2) = <s_N, w_N - R>;  :Norm  d(0.5 |w_N|^2) = <s_N, w_N>  (eval_grad_forced.jl:160-163)
-// Also returns what the Hessian's terminal part is made of: the overlaps, and with keep_s s_N itself as [2N x c] per parameter.
-struct ForcedTerminal {
-    double f = 0.0;                 // -2 / N_ess^2
-    std::vector<double> sR, sT;     // <s_N,R>, <s_N,T> of every parameter
-    std::vector<double> s;          // (keep_s) s_N of parameter p at p * 2N * c
-};
-
-static int forced_terminal(qgd_handle h, const double *sN_dev, double *grad, ForcedTerminal &t, bool keep_s = false)
-{
-    qgdk_ctx &k = h->k;
-    const size_t np = (size_t)k.n_pcof, N = k.N, L = 2 * N * k.c, hstep = (size_t)k.Np * 2 * k.cp, PWs = 2 * np * k.cp;
-    std::vector<double> sN((size_t)k.Np * PWs), gacc(np), scal(4), d, s_one(L);
-    HIP_TRY(h, hipMemcpy(sN.data(), sN_dev, sN.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if (k.cost_type) {     // :Tracking / :Norm need the final state itself: d = w_N - R, or w_N
-        std::vector<double> wN(hstep);
-        HIP_TRY(h, hipMemcpy(wN.data(), k.hist + ((size_t)k.nt - 1) * hstep, hstep * sizeof(double), hipMemcpyDeviceToHost));
-        d.resize(L);
-        unpack_panel(d.data(), 2 * N, wN.data(), 2 * k.cp, k.N, k.c);
-        if (k.cost_type == QGD_COST_TRACKING) for (size_t e = 0; e < L; e++) d[e] -= h->target_host[e];
-    }
-    HIP_TRY(h, hipMemcpy(gacc.data(), k.fs_gacc, sizeof(double) * np, hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(scal.data(), k.scal, 3 * sizeof(double), hipMemcpyDeviceToHost));
-    const double a = scal[0], b = scal[1];
-    t.f = -2.0 / ((double)k.n_ess * k.n_ess);
-    t.sR.assign(np, 0.0); t.sT.assign(np, 0.0); t.s.assign(keep_s ? np * L : 0, 0.0);
-    for (size_t p = 0; p < np; p++) {
-        double *s = keep_s ? t.s.data() + p * L : s_one.data();
-        unpack_panel(s, 2 * N, sN.data() + 2 * p * k.cp, (int)PWs, k.N, k.c);
-        double sR = 0.0, sT = 0.0, sW = 0.0;
-        for (size_t col = 0; col < (size_t)k.c; col++)
-            for (size_t i = 0; i < N; i++) {
-                const size_t e = i + 2 * N * col;
-                const double sre = s[e], sim = s[N + e], rre = h->target_host[e], rim = h->target_host[N + e];
-                sR += sre * rre + sim * rim;
-                sT += sre * rim - sim * rre;
-                if (k.cost_type) sW += sre * d[e] + sim * d[N + e];
-            }
-        t.sR[p] = sR; t.sT[p] = sT;
-        if (grad) grad[p] = (k.cost_type ? sW : t.f * (a * sR + b * sT)) + gacc[p];
-    }
-    return QGD_OK;
-}
-
-
-int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, double *grad)
-{
-    if (h) drop_graph(h);
-    if (!h || !grad) return fail(h, QGD_ERR_ARGUMENT, "null argument");     // (pcof may be NULL when the tables were set directly)
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
-    qgdk_ctx &k = h->k;
-    if (!k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before qgd_eval_grad_forced");
-    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_eval_grad_forced");
-    if (h->part_world != 1) return fail(h, QGD_ERR_STATE, "partitioned handle: the forced gradient is single-GPU");
-    int rc;
-    if ((rc = run_forward(h, pcof, n_pcof))) return rc;      // (a windowed grid: every window, the state at each window start kept)
-    const int W = h->chunks_eff;
-    const size_t hstepS = (size_t)k.Np * 2 * k.n_pcof * k.cp;
-    // A windowed grid: windows in order, each forms its matrices and forward history again from its stored start state (as the
-    // adjoint pass does), the sensitivities of all parameters continue from where the previous window left them, the guard part
-    // of the gradient accumulates.  (eval_grad_forced.jl:17-194 keeps no matrices either: one forced sweep per parameter.)
-    // The sweep record differs between the grids: a resident one keeps run_forward's sweep (SWEEP_GENERAL, with its stage
-    // derivatives), a windowed one ends at SWEEP_NONE because chunk_forward's reruns go through sweep_begin.
-    for (int r = 0; r < W; r++) {
-        if (W > 1 && (rc = chunk_forward(h, pcof, n_pcof, r, true))) return rc;
-        if (r == 0) {      // (the first window is the longest)
-            if ((rc = forced_buffers(h, (size_t)k.nt, (size_t)k.scan_blocks))) return rc;
-            HIP_TRY(h, hipMemsetAsync(k.fs_bnd, 0, hstepS * sizeof(double), k.stream));
-            HIP_TRY(h, hipMemsetAsync(k.fs_gacc, 0, ((size_t)k.n_pcof + 1) * sizeof(double), k.stream));
-        }
-        if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = W == 1; }
-        { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); }
-        { PhaseTimer t(h, "forced_sweeps"); K_TRY(h, qgdk_forced_chains(&k)); }
-        if (r + 1 < W)      // s at the start of the next window
-            HIP_TRY(h, hipMemcpyAsync(k.fs_bnd, k.fs_bnd + (size_t)k.scan_blocks * hstepS, hstepS * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
-    }
-    if ((rc = check_status(h))) return rc;
-    ForcedTerminal t;
-    return forced_terminal(h, k.fs_bnd + (size_t)k.scan_blocks * hstepS, grad, t);
-}
-
-
 // eval_adjoint (forward_evolution.jl:352-483): lambda from the given terminal condition lambda_N and forcing, no forward
 // history (none is read).  A windowed grid runs its windows in reverse; each forms its matrices, takes its slice of the forcing
 // and the y the next window ended in (the last one: y_N = L_N^H lambda_N), and writes its share of lambda_history (global time
@@ -896,233 +783,6 @@ int qgd_cols_adjoint(qgd_handle h, int32_t keep_scalars)
     if ((rc = adjoint_end(h))) return rc;
     // the final all-reduce sums [grad | scalars]; the scalars are global already: all ranks but one contribute zeros
     if (!keep_scalars) HIP_TRY(h, hipMemsetAsync(k.scal, 0, 3 * sizeof(double), k.stream));
-    return QGD_OK;
-}
-
-
-// exact Hessian of the objective: the adjoint evaluation (lambda), the forced sweep with its history
-// of sensitivities kept, then the second-order contraction of qgd_k_hessian.hip.  The terminal part is host arithmetic on s_N.
-int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *hess, double *grad)
-{
-    if (h) drop_graph(h);
-    if (!h || !hess) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
-    qgdk_ctx &k = h->k;
-    if (h->part_world != 1 || h->comm) return fail(h, QGD_ERR_STATE, "partitioned handle: the Hessian is single-GPU");
-    if (!k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before qgd_eval_hessian");
-    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_eval_hessian");
-    if (!pcof) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian needs pcof: with control tables set directly the second derivative of the controls is unknown");
-    if (n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
-    if (h->chunks_eff > 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian needs the whole time grid resident (this handle processes it in windows)");
-    if (k.N > 64) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian supports N <= 64");
-    if (k.n_ops < 1 || k.n_ops * 2 * k.m > 64) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian needs 1 <= 2 * n_ops * order/2 <= 64 basis directions");
-    const size_t nt = k.nt, np = (size_t)k.n_pcof, NB = (size_t)k.n_ops * 2 * k.m, gpc = (size_t)k.cp / 8;
-    const size_t hstep = (size_t)k.Np * 2 * k.cp, cpS = np * k.cp, hstepS = (size_t)k.Np * 2 * cpS;
-    const size_t n_shist = nt * hstepS, n_ws = k.have_guard == 1 ? n_shist : 0, n_Z = nt * NB * hstep, n_half = nt * gpc * NB * NB;
-    const size_t n_slab = nt * gpc * qgdk_hess_slab(k.Np, k.m, k.n_ops), n_zt = nt * NB * np;
-    const size_t n_Y = 2 * np * np + (k.have_guard ? qgdk_hess_gram_part((int)np, (int)nt) : 0);
-    const size_t key = ((nt * 1000003u + np) * 4099u + NB) * 2u + (n_ws ? 1u : 0u);
-    if (h->hess_key != key) {
-        free_pool(h->hess_bufs); h->hess_key = 0;
-        // everything this call allocates: its own buffers and, when they are not there yet, the forced gradient's (forced_buffers)
-        size_t bytes = (n_shist + n_ws + n_Z + n_half + n_slab + n_zt + n_Y) * sizeof(double);
-        (void)forced_buffers(h, nt, k.scan_blocks, &bytes);
-        size_t fr = 0, tot = 0;
-        if ((h->mem_budget && bytes > h->mem_budget) || (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr))
-            return fail(h, QGD_ERR_MEMORY, "the sensitivity history of qgd_eval_hessian does not fit (" + std::to_string(bytes) + " bytes needed)");
-        int rc;
-        if ((rc = dev_alloc(h, h->hess_bufs, &h->hs_shist, n_shist)) ||
-            (n_ws && (rc = dev_alloc(h, h->hess_bufs, &h->hs_ws, n_ws))) ||
-            (rc = dev_alloc(h, h->hess_bufs, &h->hs_Z, n_Z)) || (rc = dev_alloc(h, h->hess_bufs, &h->hs_half, n_half)) ||
-            (rc = dev_alloc(h, h->hess_bufs, &h->hs_slab, n_slab)) || (rc = dev_alloc(h, h->hess_bufs, &h->hs_zt, n_zt)) ||
-            (rc = dev_alloc(h, h->hess_bufs, &h->hs_Y, n_Y))) { free_pool(h->hess_bufs); return rc; }
-        if (!n_ws) h->hs_ws = nullptr;
-        h->hess_key = key;
-    }
-    int rc;
-    if ((rc = run_forward(h, pcof, n_pcof))) return rc;
-    if ((rc = adjoint_begin(h))) return rc;      // lambda (and the adjoint gradient, unused)
-    if ((rc = adjoint_end(h))) return rc;
-    if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
-    double *shist = h->hs_shist, *ws = h->hs_ws, *Z = h->hs_Z, *half = h->hs_half, *slab = h->hs_slab, *zt = h->hs_zt, *Y = h->hs_Y;
-    double *Gm = Y + np * np, *gpartial = Y + 2 * np * np;
-    if ((rc = forced_buffers(h, nt, k.scan_blocks))) return rc;
-    HIP_TRY(h, hipMemsetAsync(k.fs_bnd, 0, hstepS * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(k.fs_gacc, 0, (np + 1) * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(shist, 0, hstepS * sizeof(double), k.stream));      // s_0 = 0
-    HIP_TRY(h, hipMemsetAsync(Gm, 0, np * np * sizeof(double), k.stream));
-    { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); }
-    k.fs_shist = shist;
-    { PhaseTimer t(h, "forced_sweeps"); rc = qgdk_forced_chains(&k); }
-    k.fs_shist = nullptr;
-    if (rc) return fail(h, QGD_ERR_NO_DEVICE, std::string("kernel launch failed: qgdk_forced_chains: ") + hipGetErrorString((hipError_t)rc));
-    { PhaseTimer t(h, "hess_terms"); K_TRY(h, qgdk_hess_kernels(&k, shist, Z, half, slab, zt, Y)); }
-    if (k.have_guard) { PhaseTimer t(h, "hess_guard"); K_TRY(h, qgdk_hess_gram(&k, shist, ws, gpartial, Gm)); }
-    if ((rc = check_status(h))) return rc;
-    // terminal part: the overlaps <s_N,R>, <s_N,T> of every parameter (:Infidelity) or s_N itself (:Tracking / :Norm)
-    ForcedTerminal t;
-    if ((rc = forced_terminal(h, shist + (nt - 1) * hstepS, grad, t, k.cost_type != 0))) return rc;
-    std::vector<double> Yh(np * np), Gh(np * np);
-    HIP_TRY(h, hipMemcpy(Yh.data(), Y, np * np * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(Gh.data(), Gm, np * np * sizeof(double), hipMemcpyDeviceToHost));
-    const size_t L = 2 * (size_t)k.N * k.c;
-    for (size_t p = 0; p < np; p++)
-        for (size_t q = 0; q < np; q++) {
-            double phi;
-            if (k.cost_type) {
-                phi = 0.0;
-                for (size_t e = 0; e < L; e++) phi += t.s[p * L + e] * t.s[q * L + e];
-            } else {
-                phi = t.f * (t.sR[p] * t.sR[q] + t.sT[p] * t.sT[q]);
-            }
-            hess[p * np + q] = (Yh[p * np + q] + Yh[q * np + p]) + Gh[p * np + q] + phi;      // (Gh: both triangles from the same sums)
-        }
-    return QGD_OK;
-}
-
-// buffers of qgd_eval_hessian_vec for the present grid, basis and guard kind (nothing depends on the number of parameters but
-// three vectors).  QGD_ERR_MEMORY is decided from what THIS call allocates: its own buffers and, when they are not there yet,
-// the forced gradient's basis responses.
-static int hvp_buffers(qgd_handle h)
-{
-    qgdk_ctx &k = h->k;
-    const size_t nt = k.nt, np = (size_t)k.n_pcof, NB = (size_t)k.n_ops * 2 * k.m, gpc = (size_t)k.cp / 8, B = (size_t)k.scan_blocks;
-    const size_t hstep = (size_t)k.Np * 2 * k.cp, hist = nt * hstep, n_ws = k.have_guard == 1 ? hist : 0;
-    const size_t key = ((((nt * 1000003u + np) * 4099u + NB) * 2u + (n_ws ? 1u : 0u)) * 1031u + B) | 1u;
-    if (h->hvp_key == key) return QGD_OK;
-    free_pool(h->hvp_bufs); h->hvp_key = 0; hvp_void(h);
-    const size_t n_Z = nt * NB * hstep, n_half = nt * gpc * NB * NB, n_slab = nt * gpc * qgdk_hess_slab(k.Np, k.m, k.n_ops);
-    const size_t n_gv = qgdk_hvp_gv_len(&k), n_part = nt * gpc * NB;
-    size_t bytes = (n_Z + n_half + n_slab + 4 * hist + n_ws + (2 * B + 1) * hstep + n_gv + hstep + n_part + 3 * np + 4 + 2) * sizeof(double);
-    (void)forced_buffers(h, nt, B, &bytes);
-    size_t fr = 0, tot = 0;
-    if ((h->mem_budget && bytes > h->mem_budget) || (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr))
-        return fail(h, QGD_ERR_MEMORY, "the buffers of qgd_eval_hessian_vec do not fit (" + std::to_string(bytes) + " bytes needed)");
-    auto &b = h->hv;
-    double *one3 = nullptr;
-    int rc;
-    if ((rc = dev_alloc(h, h->hvp_bufs, &b.Z, n_Z)) || (rc = dev_alloc(h, h->hvp_bufs, &b.half, n_half)) ||
-        (rc = dev_alloc(h, h->hvp_bufs, &b.slab, n_slab)) || (rc = dev_alloc(h, h->hvp_bufs, &b.sv, hist)) ||
-        (rc = dev_alloc(h, h->hvp_bufs, &b.F, hist)) || (rc = dev_alloc(h, h->hvp_bufs, &b.Y, hist)) ||
-        (rc = dev_alloc(h, h->hvp_bufs, &b.mu, hist)) || (n_ws && (rc = dev_alloc(h, h->hvp_bufs, &b.ws, n_ws))) ||
-        (rc = dev_alloc(h, h->hvp_bufs, &b.phi, B * hstep)) || (rc = dev_alloc(h, h->hvp_bufs, &b.bnd, (B + 1) * hstep)) ||
-        (rc = dev_alloc(h, h->hvp_bufs, &b.gvt, n_gv)) || (rc = dev_alloc(h, h->hvp_bufs, &b.term, hstep)) ||
-        (rc = dev_alloc(h, h->hvp_bufs, &b.part, n_part)) || (rc = dev_alloc(h, h->hvp_bufs, &b.v, np)) ||
-        (rc = dev_alloc(h, h->hvp_bufs, &b.gB, np)) || (rc = dev_alloc(h, h->hvp_bufs, &b.out, np)) ||
-        (rc = dev_alloc(h, h->hvp_bufs, &b.scal, (size_t)4)) || (rc = dev_alloc(h, h->hvp_bufs, &one3, (size_t)2))) {
-        free_pool(h->hvp_bufs);
-        return rc;
-    }
-    if (!n_ws) b.ws = nullptr;
-    b.one3 = one3;
-    // s_v(0) = 0 and mu_0 = 0 are never written again; the unused (M+1)-th Taylor slot of the direction table stays zero
-    const struct { int64_t goff; int32_t ncoef, poff; } one = {0, 1, 0};      // the one-operator, one-coefficient basis of the direction table
-    HIP_TRY(h, hipMemcpyAsync(one3, &one, sizeof(one), hipMemcpyHostToDevice, k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.sv, 0, hist * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.mu, 0, hist * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.Y, 0, hist * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.bnd, 0, (B + 1) * hstep * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.gvt, 0, n_gv * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.scal, 0, 4 * sizeof(double), k.stream));
-    HIP_TRY(h, hipStreamSynchronize(k.stream));      // (`one` leaves scope)
-    h->hvp_key = key;
-    return QGD_OK;
-}
-
-
-// Phi'' s_v(N) as the terminal part of the second-order adjoint's right-hand side F = -f, in panel layout:
-//   :Infidelity  +(2/N_ess^2) (<s_v,R> R + <s_v,T> T)  (forced_terminal's overlaps);   :Tracking / :Norm  -s_v(N)
-static int hvp_terminal(qgd_handle h, const double *svN_dev, double *term_dev)
-{
-    qgdk_ctx &k = h->k;
-    const size_t N = k.N, PWc = 2 * (size_t)k.cp, hstep = (size_t)k.Np * PWc, L = 2 * N * k.c;
-    std::vector<double> sN(hstep), s(L), t(L), out(hstep, 0.0);
-    HIP_TRY(h, hipMemcpyAsync(sN.data(), svN_dev, hstep * sizeof(double), hipMemcpyDeviceToHost, k.stream));
-    HIP_TRY(h, hipStreamSynchronize(k.stream));
-    unpack_panel(s.data(), 2 * N, sN.data(), (int)PWc, k.N, k.c);
-    if (k.cost_type) {
-        for (size_t e = 0; e < L; e++) t[e] = -s[e];
-    } else {
-        double sR = 0.0, sT = 0.0;
-        for (size_t col = 0; col < (size_t)k.c; col++)
-            for (size_t i = 0; i < N; i++) {
-                const size_t e = i + 2 * N * col;
-                const double sre = s[e], sim = s[N + e], rre = h->target_host[e], rim = h->target_host[N + e];
-                sR += sre * rre + sim * rim;
-                sT += sre * rim - sim * rre;
-            }
-        const double f = 2.0 / ((double)k.n_ess * k.n_ess);
-        for (size_t col = 0; col < (size_t)k.c; col++)
-            for (size_t i = 0; i < N; i++) {
-                const size_t e = i + 2 * N * col;
-                const double rre = h->target_host[e], rim = h->target_host[N + e];
-                t[e] = f * (sR * rre + sT * rim);            // T = [R_im; -R_re]
-                t[N + e] = f * (sR * rim - sT * rre);
-            }
-    }
-    pack_panel(out.data(), (int)PWc, t.data(), k.N, k.c, 2 * N);
-    HIP_TRY(h, hipMemcpyAsync(term_dev, out.data(), hstep * sizeof(double), hipMemcpyHostToDevice, k.stream));
-    HIP_TRY(h, hipStreamSynchronize(k.stream));      // (`out` leaves scope)
-    return QGD_OK;
-}
-
-
-// exact Hessian-vector products.  Setup, once per pcof and kept on the handle: forward sweep, lambda,
-// stage derivatives, forced basis responses, k_hess_basis.  Per vector: the direction table, one forced sweep, k_hvp_forcing,
-// the adjoint sweep with that forcing (mu), the gradient kernels with mu in place of lambda, k_hvp_contract.
-int qgd_eval_hessian_vec(qgd_handle h, const double *pcof, int32_t n_pcof, const double *v, int32_t n_vec, double *hv, double *grad)
-{
-    if (h) drop_graph(h);
-    if (!h || !v || !hv) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    if (n_vec < 1) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_hessian_vec needs at least one vector");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
-    qgdk_ctx &k = h->k;
-    if (h->part_world != 1 || h->comm) return fail(h, QGD_ERR_STATE, "partitioned handle: the Hessian-vector product is single-GPU");
-    if (!k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before qgd_eval_hessian_vec");
-    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_eval_hessian_vec");
-    if (!pcof) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian_vec needs pcof: with control tables set directly the second derivative of the controls is unknown");
-    if (n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
-    if (h->chunks_eff > 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian_vec needs the whole time grid resident (this handle processes it in windows)");
-    if (k.N > 64) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian_vec supports N <= 64");
-    if (k.n_ops < 1 || k.n_ops * 2 * k.m > 64) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_hessian_vec needs 1 <= 2 * n_ops * order/2 <= 64 basis directions");
-    const size_t nt = k.nt, np = (size_t)k.n_pcof, hstep = (size_t)k.Np * 2 * k.cp;
-    int rc;
-    if ((rc = hvp_buffers(h))) return rc;
-    auto &b = h->hv;
-    if (!(h->hvp_valid && h->sweep.kind == SWEEP_GENERAL && sweep_reusable(h, pcof, n_pcof))) {
-        if ((rc = run_forward(h, pcof, n_pcof))) return rc;      // (the general two-point path, as qgd_eval_hessian)
-        if ((rc = adjoint_begin(h))) return rc;                  // lambda and the adjoint gradient
-        if ((rc = adjoint_end(h))) return rc;
-        if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
-        if ((rc = forced_buffers(h, nt, k.scan_blocks))) return rc;
-        { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); }
-        { PhaseTimer t(h, "hess_basis"); K_TRY(h, qgdk_hess_basis(&k, b.Z, b.half, b.slab)); }
-        if ((rc = check_status(h))) return rc;
-        h->hvp_grad.resize(np);
-        HIP_TRY(h, hipMemcpyAsync(h->hvp_grad.data(), k.grad, np * sizeof(double), hipMemcpyDeviceToHost, k.stream));
-        HIP_TRY(h, hipStreamSynchronize(k.stream));
-        h->hvp_valid = true;
-    }
-    // the second-order adjoint runs on a copy of the context: its forcing, y and mu in the product's own buffers, so that
-    // lambda, the guard forcing and the scalars of the kept evaluation stay as they are for the next vector
-    qgdk_ctx a = k;
-    a.forcing = b.F; a.yhist = b.Y; a.lam = b.mu; a.grad = b.gB; a.scal = b.scal;
-    a.front = 0; a.fuse_terminal = 0; a.grad_accumulate = 0; a.mirror_dev = nullptr; a.mirror_ticket = nullptr;
-    for (int32_t j = 0; j < n_vec; j++) {
-        HIP_TRY(h, hipMemcpyAsync(b.v, v + (size_t)j * np, np * sizeof(double), hipMemcpyHostToDevice, k.stream));
-        { PhaseTimer t(h, "hvp_direction"); K_TRY(h, qgdk_hvp_gv(&k, b.v, b.gvt)); }
-        { PhaseTimer t(h, "hvp_sweep"); K_TRY(h, qgdk_hvp_forced_sweep(&k, b.gvt, b.one3, b.phi, b.bnd, b.sv)); }
-        if (k.have_guard == 1) { PhaseTimer t(h, "hvp_guard"); K_TRY(h, qgdk_hess_wapply(&k, b.sv, b.ws, 1)); }
-        if ((rc = hvp_terminal(h, b.sv + (nt - 1) * hstep, b.term))) return rc;
-        { PhaseTimer t(h, "hvp_forcing"); K_TRY(h, qgdk_hvp_forcing(&k, b.Z, b.half, b.sv, b.ws, b.gvt, b.term, b.F, b.part)); }
-        { PhaseTimer t(h, "hvp_adjoint"); K_TRY(h, qgdk_hvp_adjoint(&a)); }
-        { PhaseTimer t(h, "hvp_gradient"); K_TRY(h, qgdk_gradient(&a)); K_TRY(h, qgdk_hvp_contract(&k, b.part, b.gB, b.out)); }
-        HIP_TRY(h, hipMemcpyAsync(hv + (size_t)j * np, b.out, np * sizeof(double), hipMemcpyDeviceToHost, k.stream));
-        HIP_TRY(h, hipStreamSynchronize(k.stream));
-    }
-    if (grad) memcpy(grad, h->hvp_grad.data(), np * sizeof(double));
     return QGD_OK;
 }
 

@@ -1,0 +1,360 @@
+// qgd_host_sens.cpp -- host side of the C ABI (include/qgd.h), sensitivities of the state to the parameters: the forced gradient
+// (eval_grad_forced.jl:17-194), the exact Hessian and Hessian-vector products (section 4d).  The three
+// share the forced gradient's buffers, and the two second-order entry points their refusals and their setup.
+#include "qgd_host.h"
+
+using namespace qgdh;
+
+// buffers of the forced gradient for (up to) nt time points and B scan blocks.  With `bytes`: nothing is allocated, the bytes
+// a call without it would allocate are added to *bytes (0 when the buffers are there already).
+static int forced_buffers(qgd_handle h, size_t nt, size_t B, size_t *bytes = nullptr)
+{
+    qgdk_ctx &k = h->k;
+    const size_t hstep = (size_t)k.Np * 2 * k.cp, NB = (size_t)k.n_ops * 2 * k.m;
+    const size_t cpS = (size_t)k.n_pcof * k.cp, hstepS = (size_t)k.Np * 2 * cpS;
+    const size_t key = (nt * 1000003u + (size_t)k.n_pcof) * 4099u + B;
+    if (h->forced_key != key) {
+        const std::vector<Buf> plan = {
+            {&k.fs_BR, nt * NB * hstep}, {&k.fs_BL, nt * NB * hstep}, {&k.fs_phi, B * hstepS}, {&k.fs_bnd, (B + 1) * hstepS},
+            {&k.fs_gacc, (size_t)k.n_pcof + 1},
+            // (the 2m+2 work panels of k_forced_basis: LDS up to 150 KB, else an HBM slab per workgroup)
+            {&h->fsc_forced, nt * (size_t)(k.cp / 8) * (size_t)(2 * k.m + 2) * k.Np * 16, qgdk_forced_lds(k.Np, k.m) > 150 * 1024}};
+        if (bytes) { *bytes += plan_bytes(plan); return QGD_OK; }
+        h->forced_key = 0;
+        int rc = plan_alloc(h, h->forced_bufs, plan);
+        if (rc) return rc;
+        h->forced_key = key;
+    }
+    if (!bytes) k.fs_scratch = h->fsc_forced;
+    return QGD_OK;
+}
+
+
+// The pool of a second-order entry point, anew from its plan.  QGD_ERR_MEMORY is decided from what THIS call allocates: the plan
+// and, when they are not there under the right key, the forced gradient's buffers.
+static int second_order_alloc(qgd_handle h, std::vector<void *> &pool, const std::vector<Buf> &plan, const std::string &what)
+{
+    free_pool(pool);
+    size_t bytes = plan_bytes(plan), fr = 0, tot = 0;
+    (void)forced_buffers(h, (size_t)h->k.nt, (size_t)h->k.scan_blocks, &bytes);
+    if ((h->mem_budget && bytes > h->mem_budget) || (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr))
+        return fail(h, QGD_ERR_MEMORY, what + " (" + std::to_string(bytes) + " bytes needed)");
+    return plan_alloc(h, pool, plan);
+}
+
+
+// how both second-order entry points begin, and what they refuse (`name`: the entry point, `what`: its result, for the messages)
+static int second_order_enter(qgd_handle h, const double *pcof, int n_pcof, const std::string &name, const char *what)
+{
+    HIP_TRY(h, hipSetDevice(h->device));
+    NEED_GRID(h);
+    const qgdk_ctx &k = h->k;
+    if (h->part_world != 1 || h->comm) return fail(h, QGD_ERR_STATE, std::string("partitioned handle: ") + what + " is single-GPU");
+    if (!k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before " + name);
+    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before " + name);
+    if (!pcof) return fail(h, QGD_ERR_UNSUPPORTED, name + " needs pcof: with control tables set directly the second derivative of the controls is unknown");
+    if (n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
+    if (h->chunks_eff > 1) return fail(h, QGD_ERR_UNSUPPORTED, name + " needs the whole time grid resident (this handle processes it in windows)");
+    if (k.N > 64) return fail(h, QGD_ERR_UNSUPPORTED, name + " supports N <= 64");
+    if (k.n_ops < 1 || k.n_ops * 2 * k.m > 64) return fail(h, QGD_ERR_UNSUPPORTED, name + " needs 1 <= 2 * n_ops * order/2 <= 64 basis directions");
+    return QGD_OK;
+}
+
+
+// what both second-order entry points start from: the forward sweep on the general two-point path, lambda (and the adjoint
+// gradient), the stage derivatives, the forced gradient's buffers and the forced basis responses in them (fs_BR, fs_BL)
+static int second_order_setup(qgd_handle h, const double *pcof, int n_pcof)
+{
+    qgdk_ctx &k = h->k;
+    int rc;
+    if ((rc = run_forward(h, pcof, n_pcof))) return rc;
+    if ((rc = adjoint_begin(h))) return rc;
+    if ((rc = adjoint_end(h))) return rc;
+    if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
+    if ((rc = forced_buffers(h, (size_t)k.nt, (size_t)k.scan_blocks))) return rc;
+    { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); }
+    return QGD_OK;
+}
+
+
+// <s,R> and <s,T>, T = [R_im; -R_re] (infidelity.jl:13-17), of a host array s [2N x c] with the target
+static void target_overlaps(qgd_handle h, const double *s, double &sR, double &sT)
+{
+    const size_t N = h->k.N, c = h->k.c;
+    const double *R = h->target_host.data();
+    double aR = 0.0, aT = 0.0;      // (sums in registers: the references may alias the arrays)
+    for (size_t col = 0; col < c; col++)
+        for (size_t i = 0; i < N; i++) {
+            const size_t e = i + 2 * N * col;
+            const double sre = s[e], sim = s[N + e], rre = R[e], rim = R[N + e];
+            aR += sre * rre + sim * rim;
+            aT += sre * rim - sim * rre;
+        }
+    sR = aR; sT = aT;
+}
+
+
+// The terminal part of the forced gradient from s_N, the sensitivities of the final state to every parameter (sN_dev: panels
+// with parameter p in columns p * cp ..), plus the guard part the forced sweeps accumulated in fs_gacc (grad may be NULL):
+//   :Infidelity  -(2/N_ess^2) (<w_N,R> <s_N,R> + <w_N,T> <s_N,T>)
+//   :Tracking    d(0.5 |w_N - R|^2) = <s_N, w_N - R>;  :Norm  d(0.5 |w_N|^2) = <s_N, w_N>  (eval_grad_forced.jl:160-163)
+// Also returns what the Hessian's terminal part is made of: the overlaps, and with keep_s s_N itself as [2N x c] per parameter.
+struct ForcedTerminal {
+    double f = 0.0;                 // -2 / N_ess^2
+    std::vector<double> sR, sT;     // <s_N,R>, <s_N,T> of every parameter
+    std::vector<double> s;          // (keep_s) s_N of parameter p at p * 2N * c
+};
+
+static int forced_terminal(qgd_handle h, const double *sN_dev, double *grad, ForcedTerminal &t, bool keep_s = false)
+{
+    qgdk_ctx &k = h->k;
+    const size_t np = (size_t)k.n_pcof, N = k.N, L = 2 * N * k.c, hstep = (size_t)k.Np * 2 * k.cp, PWs = 2 * np * k.cp;
+    std::vector<double> sN((size_t)k.Np * PWs), gacc(np), scal(4), d, s_one(L);
+    HIP_TRY(h, hipMemcpy(sN.data(), sN_dev, sN.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (k.cost_type) {     // :Tracking / :Norm need the final state itself: d = w_N - R, or w_N
+        std::vector<double> wN(hstep);
+        HIP_TRY(h, hipMemcpy(wN.data(), k.hist + ((size_t)k.nt - 1) * hstep, hstep * sizeof(double), hipMemcpyDeviceToHost));
+        d.resize(L);
+        unpack_panel(d.data(), 2 * N, wN.data(), 2 * k.cp, k.N, k.c);
+        if (k.cost_type == QGD_COST_TRACKING) for (size_t e = 0; e < L; e++) d[e] -= h->target_host[e];
+    }
+    HIP_TRY(h, hipMemcpy(gacc.data(), k.fs_gacc, sizeof(double) * np, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(scal.data(), k.scal, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    const double a = scal[0], b = scal[1];
+    t.f = -2.0 / ((double)k.n_ess * k.n_ess);
+    t.sR.assign(np, 0.0); t.sT.assign(np, 0.0); t.s.assign(keep_s ? np * L : 0, 0.0);
+    for (size_t p = 0; p < np; p++) {
+        double *s = keep_s ? t.s.data() + p * L : s_one.data();
+        unpack_panel(s, 2 * N, sN.data() + 2 * p * k.cp, (int)PWs, k.N, k.c);
+        target_overlaps(h, s, t.sR[p], t.sT[p]);
+        double sW = 0.0;
+        for (size_t col = 0; k.cost_type && col < (size_t)k.c; col++)
+            for (size_t i = 0; i < N; i++) {
+                const size_t e = i + 2 * N * col;
+                sW += s[e] * d[e] + s[N + e] * d[N + e];
+            }
+        if (grad) grad[p] = (k.cost_type ? sW : t.f * (a * t.sR[p] + b * t.sT[p])) + gacc[p];
+    }
+    return QGD_OK;
+}
+
+
+// buffers of qgd_eval_hessian for the present grid, basis and guard kind
+static int hess_buffers(qgd_handle h)
+{
+    qgdk_ctx &k = h->k;
+    const size_t nt = k.nt, np = (size_t)k.n_pcof, NB = (size_t)k.n_ops * 2 * k.m, gpc = (size_t)k.cp / 8;
+    const size_t hstep = (size_t)k.Np * 2 * k.cp, n_shist = nt * (size_t)k.Np * 2 * np * k.cp, n_ws = k.have_guard == 1 ? n_shist : 0;
+    const size_t key = ((nt * 1000003u + np) * 4099u + NB) * 2u + (n_ws ? 1u : 0u);
+    if (h->hess_key == key) return QGD_OK;
+    auto &b = h->hs;
+    h->hess_key = 0;
+    int rc = second_order_alloc(h, h->hess_bufs, {
+        {&b.shist, n_shist}, {&b.ws, n_ws, n_ws != 0}, {&b.Z, nt * NB * hstep}, {&b.half, nt * gpc * NB * NB},
+        {&b.slab, nt * gpc * qgdk_hess_slab(k.Np, k.m, k.n_ops)}, {&b.zt, nt * NB * np},
+        {&b.Y, 2 * np * np + (k.have_guard ? qgdk_hess_gram_part((int)np, (int)nt) : 0)}},
+        "the sensitivity history of qgd_eval_hessian does not fit");
+    if (rc) return rc;
+    h->hess_key = key;
+    return QGD_OK;
+}
+
+
+// buffers of qgd_eval_hessian_vec for the present grid, basis and guard kind (nothing depends on the number of parameters but
+// three vectors)
+static int hvp_buffers(qgd_handle h)
+{
+    qgdk_ctx &k = h->k;
+    const size_t nt = k.nt, np = (size_t)k.n_pcof, NB = (size_t)k.n_ops * 2 * k.m, gpc = (size_t)k.cp / 8, B = (size_t)k.scan_blocks;
+    const size_t hstep = (size_t)k.Np * 2 * k.cp, hist = nt * hstep, n_ws = k.have_guard == 1 ? hist : 0, n_gv = qgdk_hvp_gv_len(&k);
+    const size_t key = ((((nt * 1000003u + np) * 4099u + NB) * 2u + (n_ws ? 1u : 0u)) * 1031u + B) | 1u;
+    if (h->hvp_key == key) return QGD_OK;
+    auto &b = h->hv;
+    double *one3 = nullptr;
+    h->hvp_key = 0; hvp_void(h);
+    int rc = second_order_alloc(h, h->hvp_bufs, {
+        {&b.Z, nt * NB * hstep}, {&b.half, nt * gpc * NB * NB}, {&b.slab, nt * gpc * qgdk_hess_slab(k.Np, k.m, k.n_ops)},
+        {&b.sv, hist}, {&b.F, hist}, {&b.Y, hist}, {&b.mu, hist}, {&b.ws, n_ws, n_ws != 0}, {&b.phi, B * hstep},
+        {&b.bnd, (B + 1) * hstep}, {&b.gvt, n_gv}, {&b.term, hstep}, {&b.part, nt * gpc * NB}, {&b.v, np}, {&b.gB, np},
+        {&b.out, np}, {&b.scal, 4}, {&one3, 2}},
+        "the buffers of qgd_eval_hessian_vec do not fit");
+    if (rc) return rc;
+    b.one3 = one3;
+    // s_v(0) = 0 and mu_0 = 0 are never written again; the unused (M+1)-th Taylor slot of the direction table stays zero
+    const struct { int64_t goff; int32_t ncoef, poff; } one = {0, 1, 0};      // the one-operator, one-coefficient basis of the direction table
+    HIP_TRY(h, hipMemcpyAsync(one3, &one, sizeof(one), hipMemcpyHostToDevice, k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.sv, 0, hist * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.mu, 0, hist * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.Y, 0, hist * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.bnd, 0, (B + 1) * hstep * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.gvt, 0, n_gv * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.scal, 0, 4 * sizeof(double), k.stream));
+    HIP_TRY(h, hipStreamSynchronize(k.stream));      // (`one` leaves scope)
+    h->hvp_key = key;
+    return QGD_OK;
+}
+
+
+// Phi'' s_v(N) as the terminal part of the second-order adjoint's right-hand side F = -f, in panel layout:
+//   :Infidelity  +(2/N_ess^2) (<s_v,R> R + <s_v,T> T);   :Tracking / :Norm  -s_v(N)
+static int hvp_terminal(qgd_handle h, const double *svN_dev, double *term_dev)
+{
+    qgdk_ctx &k = h->k;
+    const size_t N = k.N, PWc = 2 * (size_t)k.cp, hstep = (size_t)k.Np * PWc, L = 2 * N * k.c;
+    std::vector<double> sN(hstep), s(L), t(L), out(hstep, 0.0);
+    HIP_TRY(h, hipMemcpyAsync(sN.data(), svN_dev, hstep * sizeof(double), hipMemcpyDeviceToHost, k.stream));
+    HIP_TRY(h, hipStreamSynchronize(k.stream));
+    unpack_panel(s.data(), 2 * N, sN.data(), (int)PWc, k.N, k.c);
+    if (k.cost_type) {
+        for (size_t e = 0; e < L; e++) t[e] = -s[e];
+    } else {
+        double sR, sT;
+        target_overlaps(h, s.data(), sR, sT);
+        const double f = 2.0 / ((double)k.n_ess * k.n_ess);
+        for (size_t col = 0; col < (size_t)k.c; col++)
+            for (size_t i = 0; i < N; i++) {
+                const size_t e = i + 2 * N * col;
+                const double rre = h->target_host[e], rim = h->target_host[N + e];
+                t[e] = f * (sR * rre + sT * rim);            // T = [R_im; -R_re]
+                t[N + e] = f * (sR * rim - sT * rre);
+            }
+    }
+    pack_panel(out.data(), (int)PWc, t.data(), k.N, k.c, 2 * N);
+    HIP_TRY(h, hipMemcpyAsync(term_dev, out.data(), hstep * sizeof(double), hipMemcpyHostToDevice, k.stream));
+    HIP_TRY(h, hipStreamSynchronize(k.stream));      // (`out` leaves scope)
+    return QGD_OK;
+}
+
+
+extern "C" {
+
+int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, double *grad)
+{
+    if (h) drop_graph(h);
+    if (!h || !grad) return fail(h, QGD_ERR_ARGUMENT, "null argument");     // (pcof may be NULL when the tables were set directly)
+    HIP_TRY(h, hipSetDevice(h->device));
+    NEED_GRID(h);
+    qgdk_ctx &k = h->k;
+    if (!k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before qgd_eval_grad_forced");
+    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_eval_grad_forced");
+    if (h->part_world != 1) return fail(h, QGD_ERR_STATE, "partitioned handle: the forced gradient is single-GPU");
+    int rc;
+    if ((rc = run_forward(h, pcof, n_pcof))) return rc;      // (a windowed grid: every window, the state at each window start kept)
+    const int W = h->chunks_eff;
+    const size_t hstepS = (size_t)k.Np * 2 * k.n_pcof * k.cp;
+    // A windowed grid: windows in order, each forms its matrices and forward history again from its stored start state (as the
+    // adjoint pass does), the sensitivities of all parameters continue from where the previous window left them, the guard part
+    // of the gradient accumulates.  (eval_grad_forced.jl:17-194 keeps no matrices either: one forced sweep per parameter.)
+    // The sweep record differs between the grids: a resident one keeps run_forward's sweep (SWEEP_GENERAL, with its stage
+    // derivatives), a windowed one ends at SWEEP_NONE because chunk_forward's reruns go through sweep_begin.
+    for (int r = 0; r < W; r++) {
+        if (W > 1 && (rc = chunk_forward(h, pcof, n_pcof, r, true))) return rc;
+        if (r == 0) {      // (the first window is the longest)
+            if ((rc = forced_buffers(h, (size_t)k.nt, (size_t)k.scan_blocks))) return rc;
+            HIP_TRY(h, hipMemsetAsync(k.fs_bnd, 0, hstepS * sizeof(double), k.stream));
+            HIP_TRY(h, hipMemsetAsync(k.fs_gacc, 0, ((size_t)k.n_pcof + 1) * sizeof(double), k.stream));
+        }
+        if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = W == 1; }
+        { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); }
+        { PhaseTimer t(h, "forced_sweeps"); K_TRY(h, qgdk_forced_chains(&k)); }
+        if (r + 1 < W)      // s at the start of the next window
+            HIP_TRY(h, hipMemcpyAsync(k.fs_bnd, k.fs_bnd + (size_t)k.scan_blocks * hstepS, hstepS * sizeof(double), hipMemcpyDeviceToDevice, k.stream));
+    }
+    if ((rc = check_status(h))) return rc;
+    ForcedTerminal t;
+    return forced_terminal(h, k.fs_bnd + (size_t)k.scan_blocks * hstepS, grad, t);
+}
+
+
+// exact Hessian of the objective: the adjoint evaluation (lambda), the forced sweep with its history
+// of sensitivities kept, then the second-order contraction of qgd_k_hessian.hip.  The terminal part is host arithmetic on s_N.
+int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *hess, double *grad)
+{
+    if (h) drop_graph(h);
+    if (!h || !hess) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    qgdk_ctx &k = h->k;
+    int rc;
+    if ((rc = second_order_enter(h, pcof, n_pcof, "qgd_eval_hessian", "the Hessian"))) return rc;
+    if ((rc = hess_buffers(h))) return rc;
+    if ((rc = second_order_setup(h, pcof, n_pcof))) return rc;      // (lambda; the adjoint gradient is unused)
+    const size_t nt = k.nt, np = (size_t)k.n_pcof, hstepS = (size_t)k.Np * 2 * np * k.cp;
+    const auto &b = h->hs;
+    double *Gm = b.Y + np * np, *gpartial = b.Y + 2 * np * np;
+    HIP_TRY(h, hipMemsetAsync(k.fs_bnd, 0, hstepS * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(k.fs_gacc, 0, (np + 1) * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.shist, 0, hstepS * sizeof(double), k.stream));      // s_0 = 0
+    HIP_TRY(h, hipMemsetAsync(Gm, 0, np * np * sizeof(double), k.stream));
+    k.fs_shist = b.shist;
+    { PhaseTimer t(h, "forced_sweeps"); rc = qgdk_forced_chains(&k); }
+    k.fs_shist = nullptr;
+    if (rc) return fail(h, QGD_ERR_NO_DEVICE, std::string("kernel launch failed: qgdk_forced_chains: ") + hipGetErrorString((hipError_t)rc));
+    { PhaseTimer t(h, "hess_terms"); K_TRY(h, qgdk_hess_kernels(&k, b.shist, b.Z, b.half, b.slab, b.zt, b.Y)); }
+    if (k.have_guard) { PhaseTimer t(h, "hess_guard"); K_TRY(h, qgdk_hess_gram(&k, b.shist, b.ws, gpartial, Gm)); }
+    if ((rc = check_status(h))) return rc;
+    // terminal part: the overlaps <s_N,R>, <s_N,T> of every parameter (:Infidelity) or s_N itself (:Tracking / :Norm)
+    ForcedTerminal t;
+    if ((rc = forced_terminal(h, b.shist + (nt - 1) * hstepS, grad, t, k.cost_type != 0))) return rc;
+    std::vector<double> Yh(np * np), Gh(np * np);
+    HIP_TRY(h, hipMemcpy(Yh.data(), b.Y, np * np * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(Gh.data(), Gm, np * np * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t L = 2 * (size_t)k.N * k.c;
+    for (size_t p = 0; p < np; p++)
+        for (size_t q = 0; q < np; q++) {
+            double phi;
+            if (k.cost_type) {
+                phi = 0.0;
+                for (size_t e = 0; e < L; e++) phi += t.s[p * L + e] * t.s[q * L + e];
+            } else {
+                phi = t.f * (t.sR[p] * t.sR[q] + t.sT[p] * t.sT[q]);
+            }
+            hess[p * np + q] = (Yh[p * np + q] + Yh[q * np + p]) + Gh[p * np + q] + phi;      // (Gh: both triangles from the same sums)
+        }
+    return QGD_OK;
+}
+
+
+// exact Hessian-vector products.  Setup, once per pcof and kept on the handle: forward sweep, lambda,
+// stage derivatives, forced basis responses, k_hess_basis.  Per vector: the direction table, one forced sweep, k_hvp_forcing,
+// the adjoint sweep with that forcing (mu), the gradient kernels with mu in place of lambda, k_hvp_contract.
+int qgd_eval_hessian_vec(qgd_handle h, const double *pcof, int32_t n_pcof, const double *v, int32_t n_vec, double *hv, double *grad)
+{
+    if (h) drop_graph(h);
+    if (!h || !v || !hv) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    if (n_vec < 1) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_hessian_vec needs at least one vector");
+    qgdk_ctx &k = h->k;
+    int rc;
+    if ((rc = second_order_enter(h, pcof, n_pcof, "qgd_eval_hessian_vec", "the Hessian-vector product"))) return rc;
+    const size_t nt = k.nt, np = (size_t)k.n_pcof, hstep = (size_t)k.Np * 2 * k.cp;
+    if ((rc = hvp_buffers(h))) return rc;
+    auto &b = h->hv;
+    if (!(h->hvp_valid && h->sweep.kind == SWEEP_GENERAL && sweep_reusable(h, pcof, n_pcof))) {
+        if ((rc = second_order_setup(h, pcof, n_pcof))) return rc;
+        { PhaseTimer t(h, "hess_basis"); K_TRY(h, qgdk_hess_basis(&k, b.Z, b.half, b.slab)); }
+        if ((rc = check_status(h))) return rc;
+        h->hvp_grad.resize(np);
+        HIP_TRY(h, hipMemcpyAsync(h->hvp_grad.data(), k.grad, np * sizeof(double), hipMemcpyDeviceToHost, k.stream));
+        HIP_TRY(h, hipStreamSynchronize(k.stream));
+        h->hvp_valid = true;
+    }
+    // the second-order adjoint runs on a copy of the context: its forcing, y and mu in the product's own buffers, so that
+    // lambda, the guard forcing and the scalars of the kept evaluation stay as they are for the next vector
+    qgdk_ctx a = k;
+    a.forcing = b.F; a.yhist = b.Y; a.lam = b.mu; a.grad = b.gB; a.scal = b.scal;
+    a.front = 0; a.fuse_terminal = 0; a.grad_accumulate = 0; a.mirror_dev = nullptr; a.mirror_ticket = nullptr;
+    for (int32_t j = 0; j < n_vec; j++) {
+        HIP_TRY(h, hipMemcpyAsync(b.v, v + (size_t)j * np, np * sizeof(double), hipMemcpyHostToDevice, k.stream));
+        { PhaseTimer t(h, "hvp_direction"); K_TRY(h, qgdk_hvp_gv(&k, b.v, b.gvt)); }
+        { PhaseTimer t(h, "hvp_sweep"); K_TRY(h, qgdk_hvp_forced_sweep(&k, b.gvt, b.one3, b.phi, b.bnd, b.sv)); }
+        if (k.have_guard == 1) { PhaseTimer t(h, "hvp_guard"); K_TRY(h, qgdk_hess_wapply(&k, b.sv, b.ws, 1)); }
+        if ((rc = hvp_terminal(h, b.sv + (nt - 1) * hstep, b.term))) return rc;
+        { PhaseTimer t(h, "hvp_forcing"); K_TRY(h, qgdk_hvp_forcing(&k, b.Z, b.half, b.sv, b.ws, b.gvt, b.term, b.F, b.part)); }
+        { PhaseTimer t(h, "hvp_adjoint"); K_TRY(h, qgdk_hvp_adjoint(&a)); }
+        { PhaseTimer t(h, "hvp_gradient"); K_TRY(h, qgdk_gradient(&a)); K_TRY(h, qgdk_hvp_contract(&k, b.part, b.gB, b.out)); }
+        HIP_TRY(h, hipMemcpyAsync(hv + (size_t)j * np, b.out, np * sizeof(double), hipMemcpyDeviceToHost, k.stream));
+        HIP_TRY(h, hipStreamSynchronize(k.stream));
+    }
+    if (grad) memcpy(grad, h->hvp_grad.data(), np * sizeof(double));
+    return QGD_OK;
+}
+
+}  // extern "C"

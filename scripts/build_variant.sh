@@ -15,7 +15,7 @@ for k in qgd_k_build qgd_k_inverse qgd_k_chain qgd_k_grad qgd_k_sparse qgd_k_for
   F="$FLAGS"; if [ -n "$ONLY" ] && ! echo " $ONLY " | grep -q " $k "; then F=""; fi
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function $F -I$SRC -I$ROOT/include -c $SRC/$k.hip -o $B/$k.o &
 done
-for k in qgd_host_alloc qgd_host_eval qgd_host_output qgd_host_windows qgd_host_comm; do
+for k in qgd_host_alloc qgd_host_eval qgd_host_sens qgd_host_output qgd_host_windows qgd_host_comm; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function -I$SRC -I$ROOT/include -c $SRC/$k.cpp -o $B/$k.o &
 done
 wait

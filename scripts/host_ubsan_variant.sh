@@ -9,7 +9,7 @@ OUT=$ROOT/scripts/ubench/bin
 B=$OUT/_build_ubsan
 mkdir -p $B
 cp $SRC/_build/qgd_k_*.o $B/
-for k in qgd_host_alloc qgd_host_eval qgd_host_output qgd_host_windows qgd_host_comm; do
+for k in qgd_host_alloc qgd_host_eval qgd_host_sens qgd_host_output qgd_host_windows qgd_host_comm; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -Wno-unused-function -Wno-option-ignored -fsanitize=undefined -fno-sanitize=vptr -I$SRC -I$ROOT/include -c $SRC/$k.cpp -o $B/$k.o &
 done
 wait

@@ -1,5 +1,9 @@
 """GPU tests of the exact Hessian (qgd_eval_hessian): against the numpy statement (proto_hessian.py),
-against differences of the device gradient for every cost type, symmetry, reproducibility, and the refusals."""
+against differences of the device gradient for every cost type, symmetry, reproducibility, the refusals, and the buffers
+the forced gradient, the Hessian and the Hessian-vector product keep on a handle: that they follow the grid and the control
+basis, and that the byte count of a QGD_ERR_MEMORY refusal is the amount that decides it."""
+import re
+
 import numpy as np
 import pytest
 
@@ -156,3 +160,82 @@ def test_hessian_refusals(qgd):
         assert np.array_equal(dp.discrete_adjoint(pcof)[0], g0)
     finally:
         dp.close()
+
+
+def _sensitivities(dp, pcof, V):
+    grad_h, grad_v = np.zeros(len(pcof)), np.zeros(len(pcof))
+    return (dp.eval_grad_forced(pcof), dp.eval_hessian(pcof, grad=grad_h), grad_h, dp.eval_hessian_vec(pcof, V, grad=grad_v), grad_v)
+
+
+@pytest.mark.parametrize("name,order", [("cnot2", 4), ("guarded", 6)])
+def test_sensitivity_buffers_follow_grid_and_basis(qgd, name, order):
+    prob, ctrl, pcof, target = _case(qgd, name)
+    ctrl2 = [qgd.CarrierControl(qgd.FortranBSplineControl(2, 6, prob.tf), [0.0, -1.0]) for _ in range(prob.N_operators)]
+    pcof2 = 0.05 * (0.5 - np.random.default_rng(6).random(qgd.get_number_of_control_parameters(ctrl2)))
+    assert len(pcof2) != len(pcof)
+    rng = np.random.default_rng(12)
+    V, V2 = rng.standard_normal((len(pcof), 2)), rng.standard_normal((len(pcof2), 2))
+
+    def configure(d, stage):                          # stage 0: as created; 1: the grid allocated anew; 2: another basis
+        if stage >= 1:
+            d.set_memory_budget(1 << 30)              # (room for one window and for every buffer of the three calls)
+        d.set_controls(ctrl2 if stage == 2 else ctrl); d.set_target(target)
+        assert d.memory_plan()["windows"] == 1
+
+    dp = qgd.DeviceProblem(prob, order)
+    try:
+        for stage in range(3):
+            if stage != 2:                            # (stage 2 keeps the grid of stage 1)
+                configure(dp, stage)
+            else:
+                dp.set_controls(ctrl2)
+            args = (pcof2, V2) if stage == 2 else (pcof, V)
+            got = _sensitivities(dp, *args)
+            fresh = qgd.DeviceProblem(prob, order)
+            try:
+                configure(fresh, stage)
+                ref = _sensitivities(fresh, *args)
+            finally:
+                fresh.close()
+            for i, (a, b) in enumerate(zip(got, ref)):
+                assert np.array_equal(a, b), (stage, i)
+    finally:
+        dp.close()
+
+
+@pytest.mark.parametrize("entry", ["eval_hessian", "eval_hessian_vec"])
+def test_memory_refusal_reports_the_deciding_byte_count(qgd, entry):
+    """cnot3, 20 steps, order 8 (8 initial conditions).  The precondition need > window_bytes holds at this shape for both
+    entry points (asserted below): nothing had to be raised."""
+    L = qgd._lib
+    prob, ctrl, pcof, target = cases.cnot3_case(qgd, nsteps=20, tf=20.0)
+    v = np.random.default_rng(3).standard_normal(len(pcof))
+
+    def call(d):
+        return d.eval_hessian(pcof) if entry == "eval_hessian" else d.eval_hessian_vec(pcof, v)
+
+    def run(budget):                                  # (result, None), or (None, the bytes the QGD_ERR_MEMORY refusal names)
+        d = qgd.DeviceProblem(prob, 8)
+        try:
+            window = d.memory_plan()["window_bytes"]
+            if budget is not None:
+                d.set_memory_budget(window if budget == "window" else budget)
+            d.set_controls(ctrl); d.set_target(target)
+            assert d.memory_plan()["windows"] == 1
+            try:
+                return call(d), None, window
+            except L.QGDError as e:
+                assert e.code == L.QGD_ERR_MEMORY
+                return None, int(re.search(r"\((\d+) bytes needed\)", d.lib.qgd_last_error(d.h).decode()).group(1)), window
+        finally:
+            d.close()
+
+    out, need, window = run("window")
+    assert out is None and need is not None
+    print(f"{entry}: {need} bytes needed, window {window} bytes")
+    assert need > window                              # (else a budget of `need` would not keep the grid in one window)
+    ref, _, _ = run(None)
+    out, refused, _ = run(need)
+    assert refused is None and np.array_equal(out, ref)
+    out, refused, _ = run(need - 1)
+    assert out is None and refused == need

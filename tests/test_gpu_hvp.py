@@ -188,6 +188,7 @@ def test_hvp_interleaves_with_other_entry_points(qgd, name, order):
         "hessian": lambda d: d.eval_hessian(pcof),
         "adjoint": lambda d: d.discrete_adjoint(pcof, history_precomputed=1)[0],
         "hvp": lambda d: d.eval_hessian_vec(pcof, v),
+        "forced": lambda d: d.eval_grad_forced(pcof),
     }
     alone = {}
     for key, fn in calls.items():
