@@ -164,8 +164,9 @@ int qgd_eval_forward(qgd_handle h, const double *pcof, int32_t n_pcof,
 int qgd_set_save_every(qgd_handle h, int32_t save_every_nsteps);
 
 /* The state trajectory alone, and what one looks at after a forward run: the level populations along the sweep
- * (get_populations, src/state_vector_helpers.jl:10-52, which the reference applies to a downloaded uv_history).  Both run the
- * forward sweep as the call above does, form no stage derivatives and download nothing but their output; both honour
+ * (get_populations, src/state_vector_helpers.jl:10-52, which the reference applies to a downloaded uv_history) and the
+ * expectation values of observables that are not diagonal in the level basis.  All run the
+ * forward sweep as the call above does, form no stage derivatives and download nothing but their output; all honour
  * qgd_set_save_every (n_slots = 1 + nsteps / s), take pcof == NULL when tables were set directly, fill out3 (nullable) as
  * the call above, accept registered and unregistered output arrays, work on resident and windowed time grids
  * (qgd_set_memory_budget: the output is filled window by window) and leave the stored forward sweep as the call above without
@@ -178,12 +179,21 @@ int qgd_set_save_every(qgd_handle h, int32_t save_every_nsteps);
  *                bits on every run.  history_precomputed != 0: the device's stored forward sweep is reused under the rule of
  *                the gradient call below (same pcof bitwise, else the sweep is redone; a windowed grid always redoes it;
  *                QGD_ERR_STATE when there is no previous forward evaluation).
- * QGD_ERR_ARGUMENT, before anything is launched: NULL output, level_map given with n_groups < 1.  QGD_ERR_UNSUPPORTED: a
- * handle with a communicator or a partition (these two calls are single-GPU). */
+ *   expect       [n_obs, n_slots, n_cols]: E[j, s, col] = Re(psi^H O_j psi), psi = u + iv, for n_obs observables given as planes
+ *                obs_re, obs_im [N, N, n_obs] column-major, O_j = obs_re[:, :, j] + i obs_im[:, :, j]; obs_im NULL: real
+ *                observables.  Hermiticity is not tested: the call returns the expectation value of the Hermitian part of
+ *                what was passed (the symmetric part of obs_re, the antisymmetric part of obs_im).  Not in the reference,
+ *                whose get_populations covers the observables that are diagonal in the level basis.  Summed in a fixed order
+ *                on the device: the same bits on every run, and a batch returns what single calls return.
+ *                history_precomputed as for populations.
+ * QGD_ERR_ARGUMENT, before anything is launched: NULL output, level_map given with n_groups < 1, NULL obs_re, n_obs < 1.
+ * QGD_ERR_UNSUPPORTED: a handle with a communicator or a partition (these three calls are single-GPU). */
 int qgd_eval_states(qgd_handle h, const double *pcof, int32_t n_pcof, const double *forcing,
                     double *states, double *out3);
 int qgd_eval_populations(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
                          const double *level_map, int32_t n_groups, double *populations, double *out3);
+int qgd_eval_expectations(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
+                          const double *obs_re, const double *obs_im, int32_t n_obs, double *expect, double *out3);
 
 /* discrete_adjoint! (eval_grad_discrete_adjoint.jl:107-160): gradient of
  * infidelity + guard penalty (no ridge term, as the reference).  With

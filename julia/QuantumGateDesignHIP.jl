@@ -241,6 +241,40 @@ function hip_get_populations(prob::SchrodingerProb, controls, pcof::Vector{Float
     return populations
 end
 
+"Expectation values real(psi' * O_j * psi) of Hermitian observables along the forward sweep, [n_obs, 1+div(nsteps,s),
+N_initial_conditions], formed on the device (qgd_eval_expectations): what get_populations cannot give because it is not diagonal
+in the level basis.  `observables`: one N x N matrix or a vector of them, real or complex; a matrix that is not Hermitian is
+refused (the library itself would return the expectation of its Hermitian part).  history_precomputed: reuse the device's forward
+sweep when it belongs to this pcof."
+function hip_eval_expectations(prob::SchrodingerProb, controls, pcof::Vector{Float64}, observables; order::Int=2,
+                               saveEveryNsteps::Int=1, history_precomputed::Bool=false)
+    obs = observables isa AbstractMatrix ? [observables] : collect(observables)
+    N, n_obs = prob.N_tot_levels, length(obs)
+    n_obs >= 1 || throw(ArgumentError("no observable"))
+    obs_re, obs_im = zeros(N, N, n_obs), zeros(N, N, n_obs)
+    for (j, o) in enumerate(obs)
+        size(o) == (N, N) || throw(DimensionMismatch("observable $j must be [$N, $N]"))
+        O = Matrix{ComplexF64}(o)
+        maximum(abs, O - O') <= 1e-12 * max(1.0, maximum(abs, O)) || throw(ArgumentError("observable $j is not Hermitian"))
+        obs_re[:, :, j] = real(O); obs_im[:, :, j] = imag(O)
+    end
+    has_im = any(!iszero, obs_im)
+    dp = device_problem(prob, order)
+    set_cost_type!(dp, :Infidelity)
+    pc_ptr, pc_len = set_controls!(dp, prob, controls, pcof)
+    expect = zeros(n_obs, 1 + div(prob.nsteps, saveEveryNsteps), prob.N_initial_conditions)
+    check(dp.handle, ccall((:qgd_set_save_every, libqgd), Cint, (Ptr{Cvoid}, Int32), dp.handle, saveEveryNsteps))
+    try
+        GC.@preserve pcof obs_re obs_im check(dp.handle, ccall((:qgd_eval_expectations, libqgd), Cint,
+              (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+              dp.handle, pc_ptr, pc_len, history_precomputed ? 1 : 0, pointer(obs_re), has_im ? pointer(obs_im) : C_NULL,
+              n_obs, expect, dp.last_out3))
+    finally
+        ccall((:qgd_set_save_every, libqgd), Cint, (Ptr{Cvoid}, Int32), dp.handle, 1)
+    end
+    return expect
+end
+
 "(infidelity, guard penalty) of the last evaluation of (prob, order) -- with :Tracking / :Norm: (cost, guard penalty)."
 function last_objective(prob::SchrodingerProb, order::Integer)
     dp = device_problem(prob, order)

@@ -231,6 +231,10 @@ int qgdk_layout(const qgdk_ctx *c, const double *panels, long long src_n, long l
    u^2 + v^2 (map_dev null) or n_groups sums over the levels weighted by map_dev[n_groups x N] (column-major, fixed order) */
 int qgdk_populations(const qgdk_ctx *c, const double *panels, long long src_n, double *out, long long dst_col,
                      long long dst_n, int n_cnt, const double *map_dev, int n_groups, hipStream_t stream);
+/* the same panels -> out[col][slot][n_obs], Re(psi^H O_j psi) of the n_obs observables O_j = A + iB whose planes lie in obs_re / obs_im
+   ([N x N x n_obs] column-major on the device; obs_im null: real symmetric observables), summed in a fixed order */
+int qgdk_expectations(const qgdk_ctx *c, const double *panels, long long src_n, double *out, long long dst_col,
+                      long long dst_n, int n_cnt, const double *obs_re, const double *obs_im, int n_obs, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -143,10 +143,11 @@ struct qgd_handle_s {
     std::vector<HostReg> regs;
     std::vector<void *> stage_bufs;
     double *stage_hist = nullptr, *stage_lam = nullptr, *stage_f = nullptr;
-    // qgd_eval_states / qgd_eval_populations: compact staging buffer [rows, slots, c] and the caller's level map on the device
-    // (both in stage_bufs, grown to the largest request so far)
-    double *stage_obs = nullptr, *obs_map = nullptr;
-    size_t stage_obs_len = 0, obs_map_len = 0;
+    // qgd_eval_states / qgd_eval_populations / qgd_eval_expectations: compact staging buffer [rows, slots, c], the caller's level
+    // map and the planes of the caller's observables ([N, N, n_obs] real parts, then as many imaginary parts when there are
+    // any) on the device (all in stage_bufs, grown to the largest request so far)
+    double *stage_obs = nullptr, *obs_map = nullptr, *obs_planes = nullptr;
+    size_t stage_obs_len = 0, obs_map_len = 0, obs_planes_len = 0;
     // qgd_set_lambda_derivatives: the m derivative columns of lambda_history as the reference leaves them
     bool lambda_derivs = false;
     double *dlam = nullptr, *dlam_scratch = nullptr, *stage_lam_full = nullptr;
@@ -356,10 +357,12 @@ struct RcclApi {
 
 RcclApi &rccl();
 
-// What qgd_eval_states / qgd_eval_populations take out of the state panels of a sweep: the states themselves [2N, slots, c],
-// the level populations [N, slots, c] (n_groups = 0) or their contraction with the level map on the device [n_groups, slots, c]
-enum ObserveKind { OBS_STATES, OBS_POPULATIONS };
-struct Observe { ObserveKind kind; int n_groups; double *out; };
+// What qgd_eval_states / qgd_eval_populations / qgd_eval_expectations take out of the state panels of a sweep: the states
+// themselves [2N, slots, c], the level populations [N, slots, c] (n_groups = 0) or their contraction with the level map on the
+// device [n_groups, slots, c], or the expectation values [n_obs, slots, c] of the observables whose planes lie in obs_planes
+// (obs_im: imaginary planes behind the real ones)
+enum ObserveKind { OBS_STATES, OBS_POPULATIONS, OBS_EXPECTATIONS };
+struct Observe { ObserveKind kind; int n_groups; double *out; int n_obs; bool obs_im; };
 
 // A buffer plan: the device buffers of a keyed pool, each listed once -- where its pointer goes, its length in doubles, whether
 // this problem has it (else the pointer is set to NULL).  plan_bytes: what the plan asks for (without dev_alloc's pad);

@@ -204,7 +204,7 @@ int alloc_grid(qgd_handle h)
     free_sensitivity_buffers(h);
     free_pool(h->forcing_bufs); h->forcing_key = 0;
     free_pool(h->stage_bufs); h->stage_hist = h->stage_lam = h->stage_f = nullptr;
-    h->stage_obs = h->obs_map = nullptr; h->stage_obs_len = h->obs_map_len = 0;
+    h->stage_obs = h->obs_map = h->obs_planes = nullptr; h->stage_obs_len = h->obs_map_len = h->obs_planes_len = 0;
     h->dlam = h->dlam_scratch = h->stage_lam_full = nullptr;
     h->chunk_state = h->carry_y = h->scal_scratch = nullptr; h->resident_window = 0;
     // ---- how much of the time grid is resident.  Everything (one window) when it fits the budget; else the grid is

@@ -509,6 +509,26 @@ int qgd_eval_populations(qgd_handle h, const double *pcof, int32_t n_pcof, int32
 }
 
 
+int qgd_eval_expectations(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
+                          const double *obs_re, const double *obs_im, int32_t n_obs, double *expect, double *out3)
+{
+    if (!h) return QGD_ERR_ARGUMENT;
+    if (!expect) return fail(h, QGD_ERR_ARGUMENT, "null output array");
+    if (!obs_re || n_obs < 1) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_expectations needs obs_re and n_obs >= 1");
+    HIP_TRY(h, hipSetDevice(h->device));
+    NEED_GRID(h);
+    if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_expectations is single-GPU: this handle has a communicator or a partition");
+    if (history_precomputed && h->sweep.kind == SWEEP_NONE)
+        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+    const size_t len = (size_t)n_obs * h->k.N * h->k.N;
+    int rc = grow_stage(h, &h->obs_planes, &h->obs_planes_len, (obs_im ? 2 : 1) * len);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->obs_planes, obs_re, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
+    if (obs_im) HIP_TRY(h, hipMemcpyAsync(h->obs_planes + len, obs_im, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
+    return observe_eval(h, pcof, n_pcof, history_precomputed, Observe{OBS_EXPECTATIONS, 0, expect, n_obs, obs_im != nullptr}, out3);
+}
+
+
 // eval_adjoint (forward_evolution.jl:352-483): lambda from the given terminal condition lambda_N and forcing, no forward
 // history (none is read).  A windowed grid runs its windows in reverse; each forms its matrices, takes its slice of the forcing
 // and the y the next window ended in (the last one: y_N = L_N^H lambda_N), and writes its share of lambda_history (global time

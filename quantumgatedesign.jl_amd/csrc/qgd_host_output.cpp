@@ -1,5 +1,5 @@
 // qgd_host_output.cpp -- host side of the C ABI (include/qgd.h), the reference-layout outputs (uv_history, lambda_history, adjoint_forcing,
-// states, populations) of a resident or a windowed grid: the copy stream, where the buffers' time points land in the caller's array, the
+// states, populations, expectation values) of a resident or a windowed grid: the copy stream, where the buffers' time points land in the caller's array, the
 // one transport of staged bytes, the output functions.
 #include "qgd_host.h"
 
@@ -228,14 +228,16 @@ int lambda_history_out(qgd_handle h, double *out)
 }
 
 
-// qgd_eval_states / qgd_eval_populations: the state panels hist [nt][Np][2cp] in the buffers -> the caller's [rows, slots, c],
-// rows = 2N (the states: Taylor index 0 of uv_history, through the same re-layout kernel), N (level populations) or n_groups
-// (populations contracted with the level map in obs_map).  No stage derivatives, a staging buffer of exactly the bytes that leave.
+// qgd_eval_states / qgd_eval_populations / qgd_eval_expectations: the state panels hist [nt][Np][2cp] in the buffers -> the
+// caller's [rows, slots, c], rows = 2N (the states: Taylor index 0 of uv_history, through the same re-layout kernel), N (level
+// populations), n_groups (populations contracted with the level map in obs_map) or n_obs (expectation values of the observables
+// in obs_planes).  No stage derivatives, a staging buffer of exactly the bytes that leave.
 int observe_out(qgd_handle h, const Observe &obs, int save)
 {
     qgdk_ctx &k = h->k;
     const size_t hstep = (size_t)k.Np * 2 * k.cp;
-    const size_t rows = obs.kind == OBS_STATES ? 2 * (size_t)k.N : (obs.n_groups > 0 ? (size_t)obs.n_groups : (size_t)k.N);
+    const size_t rows = obs.kind == OBS_STATES ? 2 * (size_t)k.N : obs.kind == OBS_EXPECTATIONS ? (size_t)obs.n_obs
+                      : (obs.n_groups > 0 ? (size_t)obs.n_groups : (size_t)k.N);
     const Span sp = span_of(h, save, 0);
     if (!sp.count) return QGD_OK;
     int rc = grow_stage(h, &h->stage_obs, &h->stage_obs_len, rows * sp.count * k.c);
@@ -243,6 +245,10 @@ int observe_out(qgd_handle h, const Observe &obs, int save)
     const double *src = k.hist + sp.first * hstep;
     if (obs.kind == OBS_STATES) {
         K_TRY(h, qgdk_layout(&k, src, (long long)(hstep * sp.stride), 0, h->stage_obs, (long long)(sp.count * rows), (long long)rows, 0, 0, (int)sp.count, 1, 0, k.stream, 0));
+    } else if (obs.kind == OBS_EXPECTATIONS) {
+        PhaseTimer t(h, "expectations");
+        K_TRY(h, qgdk_expectations(&k, src, (long long)(hstep * sp.stride), h->stage_obs, (long long)(sp.count * rows), (long long)rows, (int)sp.count,
+                                   h->obs_planes, obs.obs_im ? h->obs_planes + (size_t)obs.n_obs * k.N * k.N : nullptr, obs.n_obs, k.stream));
     } else {
         PhaseTimer t(h, "populations");
         K_TRY(h, qgdk_populations(&k, src, (long long)(hstep * sp.stride), h->stage_obs, (long long)(sp.count * rows), (long long)rows, (int)sp.count,

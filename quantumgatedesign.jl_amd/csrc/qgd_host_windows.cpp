@@ -93,7 +93,7 @@ int chunked_forward(qgd_handle h, const double *pcof, int n_pcof, double *uv_his
             { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); }
             if ((rc = history_out(h, uv_history, save))) return rc;
         }
-        if (obs && (rc = observe_out(h, *obs, save))) return rc;      // states or populations of the window, nothing else
+        if (obs && (rc = observe_out(h, *obs, save))) return rc;      // states, populations or expectation values of the window, nothing else
     }
     { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target)); }      // overlaps (and y_N) from the final state
     sweep_done(h, SWEEP_GENERAL, pcof, n_pcof);

@@ -10,6 +10,7 @@ behaviour as the reference:
   infidelity(...), infidelity_real, guard_penalty_real            infidelity.jl:7-96
   get_populations(history)                                        state_vector_helpers.jl:10-52
   eval_populations(prob, controls, pcof; order, saveEveryNsteps, level_map)   the same populations, formed on the device
+  eval_expectations(prob, controls, pcof, observables; order, saveEveryNsteps)   Re(psi^H O psi) along the sweep, on the device
 
 Julia's trailing ``!`` is spelled as a trailing underscore.  Arrays use the
 reference's column-major layouts (numpy ``order="F"``).
@@ -275,9 +276,9 @@ class DeviceProblem:
             None if uv_history is None else _vp(uv_history), _vp(out3)))
         return out3
 
-    # -- states and populations alone (qgd_eval_states / qgd_eval_populations) ---
+    # -- states, populations and expectation values alone (qgd_eval_states / qgd_eval_populations / qgd_eval_expectations) ---
     def observables_supported(self):
-        """eval_states / eval_populations are single-GPU calls: not for a handle with a communicator or a partition."""
+        """eval_states / eval_populations / eval_expectations are single-GPU calls: not for a handle with a communicator or a partition."""
         part = np.zeros(8, dtype=np.int32)
         _lib.check(self.h, self.lib.qgd_get_partition(self.h, _vp(part)))
         return part[6] == 1 and self.comm_info()["rank"] < 0
@@ -331,6 +332,22 @@ class DeviceProblem:
         _lib.check(self.h, self.lib.qgd_eval_populations(self.h, ptr, n, 1 if history_precomputed else 0,
                                                          None if lm is None else _vp(lm), rows if lm is not None else 0,
                                                          _vp(out), _vp(out3)))
+        self.last_scalars = out3
+        return out
+
+    def eval_expectations(self, observables, pcof=None, history_precomputed=False, out=None):
+        """Expectation values ``Re(psi^H O_j psi)`` of Hermitian observables along the sweep, formed on the device:
+        ``[n_obs, 1 + nsteps // save_every, n_cols]`` (Fortran order).  ``observables``: one ``[N, N]`` matrix, a sequence of
+        them or an ``[n_obs, N, N]`` stack, real or complex, dense or scipy sparse (observable_planes).
+        ``history_precomputed``: reuse the stored forward sweep when it belongs to this pcof.  The scalars of the call are left
+        in ``self.last_scalars``."""
+        re, im = observable_planes(observables, self.N)
+        shape = (re.shape[2], self._slots(), self.c)
+        out = np.zeros(shape, order="F") if out is None else _check_out(out, shape, "out")
+        out3 = np.zeros(3)
+        pc, ptr, n = self._pcof_arg(pcof)
+        _lib.check(self.h, self.lib.qgd_eval_expectations(self.h, ptr, n, 1 if history_precomputed else 0, _vp(re),
+                                                          None if im is None else _vp(im), re.shape[2], _vp(out), _vp(out3)))
         self.last_scalars = out3
         return out
 
@@ -676,6 +693,60 @@ def eval_populations(prob, controls, pcof, order=2, saveEveryNsteps=1, level_map
     dp.set_save_every(save)
     try:
         return dp.eval_populations(pcof, level_map=level_map)
+    finally:
+        dp.set_save_every(1)
+
+
+def observable_planes(observables, N):
+    """Observables for eval_expectations as the planes the library takes: ``(obs_re, obs_im)``, Fortran-ordered float64
+    ``[N, N, n_obs]`` with ``O_j = obs_re[:, :, j] + 1j * obs_im[:, :, j]``; ``obs_im`` is None when every imaginary part is
+    exactly zero.  ``observables``: one ``[N, N]`` matrix, a sequence of them or an ``[n_obs, N, N]`` stack, real or complex;
+    scipy sparse matrices are densified.  ValueError for a wrong shape, a non-numeric dtype or a matrix that is not
+    Hermitian: ``max|O - O^H| > 1e-12 max(1, max|O|)`` (the library itself returns the expectation of the Hermitian part)."""
+    def dense(o):
+        return o.toarray() if hasattr(o, "toarray") else o
+
+    obs = dense(observables)
+    if isinstance(obs, (list, tuple)):
+        obs = [np.asarray(dense(o)) for o in obs]
+        if not obs or any(o.shape != obs[0].shape for o in obs):
+            raise ValueError(f"observables must be [{N}, {N}] matrices")
+    try:
+        stack = np.asarray(obs)
+    except ValueError as e:
+        raise ValueError(f"observables must be [{N}, {N}] matrices") from e
+    if stack.dtype == bool or not np.issubdtype(stack.dtype, np.number):
+        raise ValueError(f"observables must be numeric; got dtype {stack.dtype}")
+    if stack.ndim == 2:
+        stack = stack[None]
+    if stack.ndim != 3 or stack.shape[0] < 1 or stack.shape[1:] != (N, N):
+        raise ValueError(f"observables must be one [{N}, {N}] matrix, a sequence of them or an [n_obs, {N}, {N}] stack; "
+                         f"got shape {np.shape(obs)}")
+    stack = stack.astype(np.complex128 if np.iscomplexobj(stack) else np.float64)
+    for j, o in enumerate(stack):
+        dev, size = np.abs(o - o.conj().T).max(), np.abs(o).max()
+        if not dev <= 1e-12 * max(1.0, size):      # (also refuses NaN)
+            raise ValueError(f"observable {j} is not Hermitian: max|O - O^H| = {dev:.3e}")
+    planes = np.moveaxis(stack, 0, 2)
+    re = np.asfortranarray(planes.real, dtype=np.float64)
+    im = np.asfortranarray(planes.imag, dtype=np.float64) if np.iscomplexobj(planes) and np.any(planes.imag != 0.0) else None
+    return re, im
+
+
+def eval_expectations(prob, controls, pcof, observables, order=2, saveEveryNsteps=1):
+    """Expectation values ``Re(psi^H O_j psi)`` of Hermitian observables along the forward sweep,
+    ``[n_obs, 1 + nsteps // saveEveryNsteps, N_initial_conditions]``, formed on the device from the state panels: what
+    ``get_populations`` cannot give because it is not diagonal in the level basis (Bloch components, quadratures, coherences,
+    the energy).  ``observables`` as for observable_planes.  Not in the reference."""
+    save = int(saveEveryNsteps)
+    if save < 1:
+        raise ValueError("saveEveryNsteps must be a positive integer")
+    observable_planes(observables, prob.N_tot_levels)      # (refusals before a handle is made or anything is uploaded)
+    dp = device_problem(prob, order)
+    dp.set_controls(controls)
+    dp.set_save_every(save)
+    try:
+        return dp.eval_expectations(observables, pcof)
     finally:
         dp.set_save_every(1)
 
