@@ -139,6 +139,19 @@ typedef struct qgdk_ctx {
     double *termU;      // [Np][2cp]   L_N^-H target: lambda_N = (2/N_ess^2)(a + ib) termU + h_N
 } qgdk_ctx;
 
+/* Np of the kernels whose size is a template argument (k_chain_fast, k_inverse_mfma, k_lambda_c; DISPATCH_NP in
+   qgd_kernels_common.h launches them) */
+static inline int qgdk_np_compiled(int Np) { return Np == 16 || Np == 32 || Np == 48 || Np == 64; }
+/* which optional buffers of the blocked scan a grid has: alloc_window allocates by these, qgd_k_chain.hip launches by them */
+static inline int qgdk_has_suffix(const qgdk_ctx *c)      /* SufP, SufPhi */
+{
+    return qgdk_np_compiled(c->Np) && c->scan_blocks2 > 1 && c->scan_g > 2;
+}
+static inline int qgdk_has_sub_hist(const qgdk_ctx *c)    /* Hmid, Qmid: blocks of at least 6 steps (the value of sub_hist) */
+{
+    return qgdk_np_compiled(c->Np) && c->scan_blen >= 6;
+}
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -157,18 +170,17 @@ int qgdk_propagator(const qgdk_ctx *c);
 int qgdk_propagator_is_fused(const qgdk_ctx *c);
 int qgdk_forward_blocks(const qgdk_ctx *c);
 int qgdk_forward_finish(const qgdk_ctx *c);
-int qgdk_forward_blocks_range(const qgdk_ctx *c, int b0, int b1, hipStream_t stream);
-int qgdk_forward_blocks_upper(const qgdk_ctx *c);
 int qgdk_guard(const qgdk_ctx *c);
 int qgdk_guard_is_fused(const qgdk_ctx *c);
-int qgdk_guard_parts(const qgdk_ctx *c);
-int qgdk_guard_fold(const qgdk_ctx *c);       /* scal[2] += the partials of gpart in a fixed order (windows, ranks without the final time) */      /* workgroups of the guard stage of this configuration = entries of gpart it writes */
+int qgdk_guard_parts(const qgdk_ctx *c);      /* workgroups of the guard stage of this configuration = entries of gpart it writes */
+int qgdk_guard_fold(const qgdk_ctx *c);       /* scal[2] += the partials of gpart in a fixed order (windows, ranks without the final time) */
 int qgdk_terminal_can_fuse(const qgdk_ctx *c);
 int qgdk_terminal(const qgdk_ctx *c, int write_y);
 int qgdk_terminal_given(const qgdk_ctx *c);   /* y_N from the overlaps already in scal (column shards) */
 int qgdk_adjoint_blocks(const qgdk_ctx *c);
 int qgdk_adjoint_finish(const qgdk_ctx *c);
 int qgdk_apply_LH(const qgdk_ctx *c);
+int qgdk_copy_yN_to_starts(const qgdk_ctx *c, const double *src);   /* y_N from src to every place the adjoint scan starts from */
 int qgdk_lambda(const qgdk_ctx *c);
 int qgdk_derivs(const qgdk_ctx *c);
 int qgdk_gradient(const qgdk_ctx *c);

@@ -153,9 +153,9 @@ static int alloc_window(qgd_handle h, bool dry, size_t *bytes)
         (!A(&k.phi0, hstep) || !A(&k.hforc, nt * hstep) || !A(&k.termU, hstep))) return rc;
     // sub-block history pass (qgd_k_chain.hip): only with compiled-size chains, blocks of at least 6 steps
     k.sub_hist = 0; k.sub_n = 0; if (!dry) k.Hmid = k.Qmid = k.SufP = k.SufPhi = nullptr;
-    if ((k.Np == 16 || k.Np == 32 || k.Np == 48 || k.Np == 64) && k.scan_blocks2 > 1 && k.scan_g > 2 &&
+    if (qgdk_has_suffix(&k) &&
         (!A(&k.SufP, (nb2 + 1) * (size_t)(k.scan_g - 2) * 2 * pl) || !A(&k.SufPhi, (nb2 + 1) * (size_t)(k.scan_g - 2) * hstep))) return rc;
-    if ((k.Np == 16 || k.Np == 32 || k.Np == 48 || k.Np == 64) && k.scan_blen >= 6) {
+    if (qgdk_has_sub_hist(&k)) {
         k.sub_hist = 1; k.sub_n = (k.scan_blen + 2) / 3 - 1;      // stored products after 3, 6, ... steps
         if (!A(&k.Hmid, nb * (size_t)k.sub_n * 2 * pl) || !A(&k.Qmid, (nb2 + 1) * (size_t)std::max(k.scan_g, 2) * 2 * pl)) return rc;
     }

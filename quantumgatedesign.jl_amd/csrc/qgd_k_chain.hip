@@ -1116,28 +1116,26 @@ static bool chain_is_dense(const ChainArgs &a)
 template <int MODE, int NG>
 static int launch_chain_ng(const ChainArgs &a, hipStream_t stream)
 {
-    const bool fast = (a.Np == 16 || a.Np == 32 || a.Np == 48 || a.Np == 64) && a.ngroups % NG == 0;
+    const bool fast = qgdk_np_compiled(a.Np) && a.ngroups % NG == 0;
     const int ng = fast ? a.ngroups / NG : a.ngroups;
     const int nwg = ((MODE == 0) ? 8 * ng * ((a.nblocks + 7) / 8) : a.nblocks * ng) + ((MODE == 2 && fast && a.t_on) ? 1 : 0) +
                     ((MODE == 0 && fast && a.p0_on) ? 1 : 0);
     if (nwg <= 0) return 0;
-    switch (fast ? a.Np : 0) {
-    case 16: hipLaunchKernelGGL((k_chain_fast<16, MODE, NG>), dim3(nwg), dim3(16 * 4 * CHAIN_NT(MODE)), 0, stream, a); break;
-    case 32: hipLaunchKernelGGL((k_chain_fast<32, MODE, NG>), dim3(nwg), dim3(32 * 4 * CHAIN_NT(MODE)), 0, stream, a); break;
-    case 48: hipLaunchKernelGGL((k_chain_fast<48, MODE, NG>), dim3(nwg), dim3(48 * 4 * CHAIN_NT(MODE)), 0, stream, a); break;
-    case 64:         hipLaunchKernelGGL((k_chain_fast<64, MODE, NG>), dim3(nwg), dim3(64 * 4 * CHAIN_NT(MODE)), 0, stream, a); break;
-    default: {
-        if (MODE >= 4) {
-            const size_t shm4 = (size_t)2 * a.Np * 16 * sizeof(double);
-            if (shm4 > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)k_chain_forced_generic<(MODE >= 4 ? MODE : 4)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm4));
-            hipLaunchKernelGGL((k_chain_forced_generic<(MODE >= 4 ? MODE : 4)>), dim3(a.nblocks * a.ngroups), dim3(256), shm4, stream, a);
-            return (int)hipGetLastError();
-        }
-        if (chain_is_dense(a)) return launch_chain_dense<(MODE >= 4 ? 1 : MODE)>(a, stream);
-        size_t shm = (size_t)2 * a.Np * 16 * sizeof(double);
-        hipLaunchKernelGGL((k_chain_generic<(MODE >= 4 ? 1 : MODE)>), dim3(nwg), dim3(256), shm, stream, a);
+    if (fast) {
+#define CALL_CF(N) hipLaunchKernelGGL((k_chain_fast<N, MODE, NG>), dim3(nwg), dim3(N * 4 * CHAIN_NT(MODE)), 0, stream, a)
+        DISPATCH_NP(a.Np, CALL_CF)
+#undef CALL_CF
+        return (int)hipGetLastError();
     }
+    if (MODE >= 4) {
+        const size_t shm4 = (size_t)2 * a.Np * 16 * sizeof(double);
+        if (shm4 > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)k_chain_forced_generic<(MODE >= 4 ? MODE : 4)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm4));
+        hipLaunchKernelGGL((k_chain_forced_generic<(MODE >= 4 ? MODE : 4)>), dim3(a.nblocks * a.ngroups), dim3(256), shm4, stream, a);
+        return (int)hipGetLastError();
     }
+    if (chain_is_dense(a)) return launch_chain_dense<(MODE >= 4 ? 1 : MODE)>(a, stream);
+    size_t shm = (size_t)2 * a.Np * 16 * sizeof(double);
+    hipLaunchKernelGGL((k_chain_generic<(MODE >= 4 ? 1 : MODE)>), dim3(nwg), dim3(256), shm, stream, a);
     return (int)hipGetLastError();
 }
 
@@ -1155,15 +1153,11 @@ static int launch_chain(const ChainArgs &a, hipStream_t stream)
 // history pass (MODE 6) in the same grid; falls back to the plain MODE 0 launch where MODE 6 does not apply
 static int launch_chain_level2(const ChainArgs &a0, const ChainArgs &a6, bool with_suffix, hipStream_t stream)
 {
-    const bool fast = (a0.Np == 16 || a0.Np == 32 || a0.Np == 48 || a0.Np == 64);
-    if (!with_suffix || !fast || (long long)a0.nblocks * a0.ngroups > 256) return launch_chain<0>(a0, stream);
+    if (!with_suffix || !qgdk_np_compiled(a0.Np) || (long long)a0.nblocks * a0.ngroups > 256) return launch_chain<0>(a0, stream);
     const int nA = 8 * a0.ngroups * ((a0.nblocks + 7) / 8) + (a0.p0_on ? 1 : 0), nB = 8 * a6.ngroups * ((a6.nblocks + 7) / 8);
-    switch (a0.Np) {
-    case 16: hipLaunchKernelGGL((k_chain_fast2<16, 0, 6, 1>), dim3(nA + nB), dim3(16 * 4 * CHAIN_NT(0)), 0, stream, a0, a6, nA); break;
-    case 32: hipLaunchKernelGGL((k_chain_fast2<32, 0, 6, 1>), dim3(nA + nB), dim3(32 * 4 * CHAIN_NT(0)), 0, stream, a0, a6, nA); break;
-    case 48: hipLaunchKernelGGL((k_chain_fast2<48, 0, 6, 1>), dim3(nA + nB), dim3(48 * 4 * CHAIN_NT(0)), 0, stream, a0, a6, nA); break;
-    default: hipLaunchKernelGGL((k_chain_fast2<64, 0, 6, 1>), dim3(nA + nB), dim3(64 * 4 * CHAIN_NT(0)), 0, stream, a0, a6, nA); break;
-    }
+#define CALL_CF2(N) hipLaunchKernelGGL((k_chain_fast2<N, 0, 6, 1>), dim3(nA + nB), dim3(N * 4 * CHAIN_NT(0)), 0, stream, a0, a6, nA)
+    DISPATCH_NP(a0.Np, CALL_CF2)
+#undef CALL_CF2
     return (int)hipGetLastError();
 }
 
@@ -1663,16 +1657,11 @@ __global__ __launch_bounds__(256) void k_guard_fold(const double *__restrict__ g
     if (threadIdx.x == 0) scal[2] += ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-extern "C" {
-
 #define QGD_SUB_LEN 3      /* steps per sub-block of the forward history pass */
-static inline bool chain_is_fast(const qgdk_ctx *c) { return c->Np == 16 || c->Np == 32 || c->Np == 48 || c->Np == 64; }
+static inline bool chain_is_fast(const qgdk_ctx *c) { return qgdk_np_compiled(c->Np); }
 
 // diagonal guard projector + compiled-size sweeps: k_chain_fast<.,1,.> does the guard work
-static inline bool guard_is_fused(const qgdk_ctx *c)
-{
-    return !c->front && c->have_guard == 2 && (c->Np == 16 || c->Np == 32 || c->Np == 48 || c->Np == 64);
-}
+static inline bool guard_is_fused(const qgdk_ctx *c) { return !c->front && c->have_guard == 2 && chain_is_fast(c); }
 
 // ---------------------------------------------------------------------------
 // The scan over time has three levels.  A rank owns a window of B = bpr blocks (level 1: blen steps
@@ -1686,13 +1675,93 @@ static inline bool guard_is_fused(const qgdk_ctx *c)
 // ---------------------------------------------------------------------------
 // the adjoint history pass takes the blocks after its own inside the super-block in ONE step (stored suffix products and
 // affine parts, ChainArgs::suf_P): compiled-size chains with a second scan level of more than two blocks per super-block
-static inline bool suffix_on(const qgdk_ctx *c)
-{
-    return c->SufP && c->SufPhi && chain_is_fast(c) && c->scan_blocks2 > 1 && c->scan_g > 2 && !qgd_path("no_suffix");
-}
+static inline bool suffix_on(const qgdk_ctx *c) { return c->SufP && c->SufPhi && qgdk_has_suffix(c) && !qgd_path("no_suffix"); }
 
 static inline size_t rx_chunk(const qgdk_ctx *c) { return (size_t)4 * c->Np * c->Np; }
 static inline size_t phirx_chunk(const qgdk_ctx *c) { return (size_t)2 * c->Np * 2 * c->cp; }
+
+// Every launch below starts from one of these two and then states only what is special to it.
+// nblocks chains of blen of the S matrices at Pmat each, on ngroups column groups
+static ChainArgs chain_args(const qgdk_ctx *c, const double *Pmat, int S, int nblocks, int blen, int ngroups)
+{
+    ChainArgs a{};
+    a.Np = c->Np; a.cp = c->cp; a.Pmat = Pmat; a.S = S; a.nblocks = nblocks; a.blen = blen; a.ngroups = ngroups;
+    return a;
+}
+// chains of states (MODE 1, 3, 5) on the cp / 8 column groups: block b from start + b * stride, every state into out
+static ChainArgs state_chain(const qgdk_ctx *c, const double *Pmat, int S, int nblocks, int blen, const double *start,
+                             size_t stride, double *out)
+{
+    ChainArgs a = chain_args(c, Pmat, S, nblocks, blen, c->cp / 8);
+    a.start = start; a.start_stride = (long long)stride; a.out = out;
+    return a;
+}
+
+// fused front: phi_0 = L_0 psi_0 by an extra workgroup of a MODE 0 launch
+static void phi0_rides(ChainArgs &a, const qgdk_ctx *c) { a.p0_on = 1; a.p0_E = c->L; a.p0_psi0 = c->psi0; a.p0_out = c->phi0; }
+
+// guard_is_fused: the history pass writes the adjoint forcing and the guard penalty of the states it produces
+static void fused_guard(ChainArgs &a, const qgdk_ctx *c)
+{
+    a.guard_diag = c->guard_diag; a.guard_forcing = c->forcing; a.scal = c->scal; a.gN = c->N;
+    a.gpart = c->gpart_on ? c->gpart : nullptr;
+    a.n_off = c->n_off; a.nt_glob = c->nt_glob; a.count_first = (c->n_off == 0) ? 1 : 0; a.dt = c->dt; a.tf = c->tf;
+}
+
+// the places that receive y_N, where the adjoint scan starts from: the last entry of y's history, this rank's second slot
+// of phiRX (for the other ranks), the last block and super-block boundaries
+struct YNDest { double *yhist, *slot, *bnd, *bnd2; };
+static YNDest yN_dest(const qgdk_ctx *c)
+{
+    const size_t hstep = (size_t)c->Np * 2 * c->cp;
+    return {c->yhist + (size_t)(c->nt - 1) * hstep, c->phiRX + (size_t)c->part_rank * phirx_chunk(c) + hstep,
+            c->bndY + (size_t)c->scan_blocks * hstep, c->bndY2 + (size_t)c->scan_blocks2 * hstep};
+}
+
+// What part 2 of a sweep reads and writes where every level of the scan is a launch of its own (any Np; the compiled
+// sizes take one launch).  Coarsest level first: matrices and affine parts (forward: none) of the super-blocks, the
+// blocks and the steps; states at the super-block and block boundaries; the history.  win: the chain over the other ranks'
+// windows (S = 0: this rank owns the side of the grid the sweep starts from), win_end: the state it leaves at this window.
+struct SweepLevels {
+    const double *P2, *P1, *P0, *f2, *f1, *f0;
+    double *b2, *b1, *hist;
+    ChainArgs win;
+    const double *win_end;
+};
+
+// The forward sweep (MODE 1) enters a level at entry 0 of its boundaries and block b starts from entry b; the adjoint
+// sweep (MODE 3) enters at the last entry and block b starts from entry b + 1.
+template <int MODE>
+static int sweep_levels(const qgdk_ctx *c, const SweepLevels &l)
+{
+    constexpr bool ADJ = (MODE == 3);
+    const size_t hstep = (size_t)c->Np * 2 * c->cp, first = ADJ ? hstep : 0;
+    const int B = c->scan_blocks, B2 = c->scan_blocks2, g = c->scan_g;
+    double *in1 = l.b1 + (ADJ ? (size_t)B * hstep : 0), *in2 = l.b2 + (ADJ ? (size_t)B2 * hstep : 0);
+    int rc;
+    if (l.win.S > 0) {
+        if ((rc = launch_chain<MODE>(l.win, c->stream))) return rc;
+        for (double *dst : {in1, in2, l.hist + (ADJ ? (size_t)(c->nt - 1) * hstep : 0)})
+            HIPCHK(hipMemcpyAsync(dst, l.win_end, hstep * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    if (B2 <= 1) {     // states at every block boundary
+        ChainArgs s2 = state_chain(c, l.P1, B, 1, B, in1, 0, l.b1);
+        s2.forcing = l.f1;
+        if ((rc = launch_chain<MODE>(s2, c->stream))) return rc;
+    } else {           // at the super-block boundaries, then from each of them at the block boundaries inside
+        ChainArgs b2 = state_chain(c, l.P2, B2, 1, B2, in2, 0, l.b2);
+        b2.forcing = l.f2;
+        if ((rc = launch_chain<MODE>(b2, c->stream))) return rc;
+        ChainArgs c2 = state_chain(c, l.P1, B, B2, g, l.b2 + first, hstep, l.b1);
+        c2.forcing = l.f1;
+        if ((rc = launch_chain<MODE>(c2, c->stream))) return rc;
+    }
+    ChainArgs s3 = state_chain(c, l.P0, c->nt - 1, B, c->scan_blen, l.b1 + first, hstep, l.hist);
+    s3.forcing = l.f0;
+    return launch_chain<MODE>(s3, c->stream);
+}
+
+extern "C" {
 
 // forward, part 1 (no other rank needed): block propagators, super-block propagators, window product
 int qgdk_forward_blocks(const qgdk_ctx *c)
@@ -1700,79 +1769,27 @@ int qgdk_forward_blocks(const qgdk_ctx *c)
     const size_t pl2 = (size_t)2 * c->Np * c->Np;
     const int B = c->scan_blocks, B2 = c->scan_blocks2, g = c->scan_g;
     int rc;
-    ChainArgs a{};
-    a.Np = c->Np; a.cp = c->cp; a.S = c->nt - 1; a.Pmat = c->Pc;
+    ChainArgs a = chain_args(c, c->Pc, c->nt - 1, B, c->scan_blen, c->Np / 8);
     a.PiC = c->PiX; a.PiR = c->PiX + (size_t)B * pl2;
-    a.nblocks = B; a.blen = c->scan_blen; a.ngroups = c->Np / 8;
     if (c->sub_hist) { a.mid_out = c->Hmid; a.mid_every = QGD_SUB_LEN; a.mid_first = QGD_SUB_LEN; a.mid_n = c->sub_n; }
     // fused front: phi_0 = L_0 psi_0 rides along -- in the level-2 launch where there is one (most of the chip is idle there;
     // beside the block products, one workgroup per CU, the extra workgroup cost the launch 2.4 us), else here
-    if (c->front && B2 <= 1) { a.p0_on = 1; a.p0_E = c->L; a.p0_psi0 = c->psi0; a.p0_out = c->phi0; }
+    if (c->front && B2 <= 1) phi0_rides(a, c);
     if ((rc = launch_chain<0>(a, c->stream))) return rc;
     if (B2 > 1) {      // super-block propagators from the block propagators
-        ChainArgs a2{};
-        a2.Np = c->Np; a2.cp = c->cp; a2.S = B; a2.Pmat = c->PiX;
-        a2.PiC = c->PiC2; a2.PiR = c->PiR2; a2.nblocks = B2; a2.blen = g; a2.ngroups = c->Np / 8;
-        if (c->front) { a2.p0_on = 1; a2.p0_E = c->L; a2.p0_psi0 = c->psi0; a2.p0_out = c->phi0; }
+        ChainArgs a2 = chain_args(c, c->PiX, B, B2, g, c->Np / 8);
+        a2.PiC = c->PiC2; a2.PiR = c->PiR2;
+        if (c->front) phi0_rides(a2, c);
         if (c->sub_hist && g > 2) { a2.mid_out = c->Qmid; a2.mid_every = 1; a2.mid_first = 2; a2.mid_n = g - 2; }
         // beside them (same grid, idle CUs): the suffix products of the blocks of every super-block for the adjoint history pass
         ChainArgs a6{};
         const bool suf = suffix_on(c);
-        if (suf) {
-            a6.Np = c->Np; a6.cp = c->cp; a6.S = B; a6.Pmat = c->PiX + (size_t)B * pl2; a6.nblocks = B2; a6.blen = g; a6.ngroups = c->Np / 8;
-            a6.mid_out = c->SufP; a6.mid_n = g - 2;
-        }
+        if (suf) { a6 = chain_args(c, c->PiX + (size_t)B * pl2, B, B2, g, c->Np / 8); a6.mid_out = c->SufP; a6.mid_n = g - 2; }
         if ((rc = launch_chain_level2(a2, a6, suf, c->stream))) return rc;
     }
-    if (c->part_world > 1) {   // the product of the whole window, into this rank's chunk of RX
-        ChainArgs r{};
-        r.Np = c->Np; r.cp = c->cp; r.ngroups = c->Np / 8; r.nblocks = 1;
-        if (B2 > 1) { r.S = B2; r.blen = B2; r.Pmat = c->PiC2; } else { r.S = B; r.blen = B; r.Pmat = c->PiX; }
-        r.PiC = c->RX + (size_t)c->part_rank * rx_chunk(c); r.PiR = r.PiC + pl2;
-        if ((rc = launch_chain<0>(r, c->stream))) return rc;
-    }
-    return 0;
-}
-
-// forward, part 1 in pieces (ranges of blocks): the block propagators of blocks [b0, b1) on `stream`;
-// then the levels above them (super-blocks, window product) on the context's stream
-int qgdk_forward_blocks_range(const qgdk_ctx *c, int b0, int b1, hipStream_t stream)
-{
-    const size_t pl2 = (size_t)2 * c->Np * c->Np;
-    const int B = c->scan_blocks, S = c->nt - 1;
-    const int s_lo = b0 * c->scan_blen, s_hi = (b1 * c->scan_blen < S) ? b1 * c->scan_blen : S;
-    if (b1 <= b0 || s_hi <= s_lo) return 0;
-    ChainArgs a{};
-    a.Np = c->Np; a.cp = c->cp; a.S = s_hi - s_lo; a.Pmat = c->Pc + (size_t)s_lo * pl2;
-    a.PiC = c->PiX + (size_t)b0 * pl2; a.PiR = c->PiX + ((size_t)B + b0) * pl2;
-    a.nblocks = b1 - b0; a.blen = c->scan_blen; a.ngroups = c->Np / 8;
-    if (c->sub_hist) { a.mid_out = c->Hmid + (size_t)b0 * c->sub_n * pl2; a.mid_every = QGD_SUB_LEN; a.mid_first = QGD_SUB_LEN; a.mid_n = c->sub_n; }
-    return launch_chain<0>(a, stream);
-}
-
-int qgdk_forward_blocks_upper(const qgdk_ctx *c)
-{
-    const size_t pl2 = (size_t)2 * c->Np * c->Np;
-    const int B = c->scan_blocks, B2 = c->scan_blocks2, g = c->scan_g;
-    int rc;
-    if (B2 > 1) {      // super-block propagators from the block propagators
-        ChainArgs a2{};
-        a2.Np = c->Np; a2.cp = c->cp; a2.S = B; a2.Pmat = c->PiX;
-        a2.PiC = c->PiC2; a2.PiR = c->PiR2; a2.nblocks = B2; a2.blen = g; a2.ngroups = c->Np / 8;
-        if (c->sub_hist && g > 2) { a2.mid_out = c->Qmid; a2.mid_every = 1; a2.mid_first = 2; a2.mid_n = g - 2; }
-        // beside them (same grid, idle CUs): the suffix products of the blocks of every super-block for the adjoint history pass
-        ChainArgs a6{};
-        const bool suf = suffix_on(c);
-        if (suf) {
-            a6.Np = c->Np; a6.cp = c->cp; a6.S = B; a6.Pmat = c->PiX + (size_t)B * pl2; a6.nblocks = B2; a6.blen = g; a6.ngroups = c->Np / 8;
-            a6.mid_out = c->SufP; a6.mid_n = g - 2;
-        }
-        if ((rc = launch_chain_level2(a2, a6, suf, c->stream))) return rc;
-    }
-    if (c->part_world > 1) {   // the product of the whole window, into this rank's chunk of RX
-        ChainArgs r{};
-        r.Np = c->Np; r.cp = c->cp; r.ngroups = c->Np / 8; r.nblocks = 1;
-        if (B2 > 1) { r.S = B2; r.blen = B2; r.Pmat = c->PiC2; } else { r.S = B; r.blen = B; r.Pmat = c->PiX; }
+    if (c->part_world > 1) {   // the product of the whole window (of the super-blocks where there are some), into this rank's chunk of RX
+        const int n = (B2 > 1) ? B2 : B;
+        ChainArgs r = chain_args(c, (B2 > 1) ? c->PiC2 : c->PiX, n, 1, n, c->Np / 8);
         r.PiC = c->RX + (size_t)c->part_rank * rx_chunk(c); r.PiR = r.PiC + pl2;
         if ((rc = launch_chain<0>(r, c->stream))) return rc;
     }
@@ -1785,13 +1802,10 @@ int qgdk_forward_finish(const qgdk_ctx *c)
 {
     const size_t hstep = (size_t)c->Np * 2 * c->cp;
     const int B = c->scan_blocks, B2 = c->scan_blocks2, g = c->scan_g;
-    int rc;
     if (chain_is_fast(c)) {
         // one launch: the workgroup of block b first advances psi_0 over the windows of the lower ranks, the
         // super-blocks and the blocks before b (prefix segments of k_chain_fast), then writes its history
-        ChainArgs s3{};
-        s3.Np = c->Np; s3.cp = c->cp; s3.S = c->nt - 1; s3.Pmat = c->Pc; s3.start = c->psi0; s3.start_stride = 0;
-        s3.out = c->hist; s3.nblocks = B; s3.blen = c->scan_blen; s3.ngroups = c->cp / 8;
+        ChainArgs s3 = state_chain(c, c->Pc, c->nt - 1, B, c->scan_blen, c->psi0, 0, c->hist);
         if (c->front) { s3.start = c->phi0; s3.out = c->phist; }      // fused front: the sweep runs in phi = L psi (k_psi follows)
         int q = 0;
         if (c->part_rank > 0) {
@@ -1806,48 +1820,18 @@ int qgdk_forward_finish(const qgdk_ctx *c)
             s3.nblocks = B * s3.sub_T;
             if (B2 > 1 && g > 2) { s3.pre_Q = c->Qmid; s3.pre_Qn = g - 2; }
         }
-        if (guard_is_fused(c)) {
-            s3.guard_diag = c->guard_diag; s3.guard_forcing = c->forcing; s3.scal = c->scal; s3.gN = c->N;
-            s3.gpart = c->gpart_on ? c->gpart : nullptr;
-            s3.n_off = c->n_off; s3.nt_glob = c->nt_glob; s3.count_first = (c->n_off == 0) ? 1 : 0; s3.dt = c->dt; s3.tf = c->tf;
-        }
+        if (guard_is_fused(c)) fused_guard(s3, c);
         return launch_chain<1>(s3, c->stream);
     }
-    if (c->part_rank > 0) {   // psi at the window start = R_{r-1} ... R_0 psi_0
-        ChainArgs w{};
-        w.Np = c->Np; w.cp = c->cp; w.S = c->part_rank; w.Pmat = c->RX; w.pm_bpr = 1; w.pm_chunk = (long long)rx_chunk(c);
-        w.start = c->psi0; w.start_stride = 0; w.out = c->wbnd; w.nblocks = 1; w.blen = c->part_rank; w.ngroups = c->cp / 8;
-        if ((rc = launch_chain<1>(w, c->stream))) return rc;
-        const double *ws = c->wbnd + (size_t)c->part_rank * hstep;
-        HIPCHK(hipMemcpyAsync(c->bnd, ws, hstep * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->bnd2, ws, hstep * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->hist, ws, hstep * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }   // rank 0: bnd[0] = bnd2[0] = hist[0] = psi_0 were written when the grid was allocated
-    if (B2 <= 1) {
-        ChainArgs s2{};
-        s2.Np = c->Np; s2.cp = c->cp; s2.S = B; s2.Pmat = c->PiX;
-        s2.start = c->bnd; s2.start_stride = 0; s2.out = c->bnd; s2.nblocks = 1; s2.blen = B; s2.ngroups = c->cp / 8;
-        if ((rc = launch_chain<1>(s2, c->stream))) return rc;
-    } else {
-        ChainArgs b2{};   // states at super-block starts
-        b2.Np = c->Np; b2.cp = c->cp; b2.S = B2; b2.Pmat = c->PiC2; b2.start = c->bnd2; b2.start_stride = 0; b2.out = c->bnd2;
-        b2.nblocks = 1; b2.blen = B2; b2.ngroups = c->cp / 8;
-        if ((rc = launch_chain<1>(b2, c->stream))) return rc;
-        ChainArgs c2{};   // states at every block start
-        c2.Np = c->Np; c2.cp = c->cp; c2.S = B; c2.Pmat = c->PiX;
-        c2.start = c->bnd2; c2.start_stride = (long long)hstep; c2.out = c->bnd; c2.nblocks = B2; c2.blen = g; c2.ngroups = c->cp / 8;
-        if ((rc = launch_chain<1>(c2, c->stream))) return rc;
+    // (no guard part here: guard_is_fused needs the compiled sizes, qgdk_guard launches the stand-alone kernels)
+    SweepLevels l{c->PiC2, c->PiX, c->Pc, nullptr, nullptr, nullptr, c->bnd2, c->bnd, c->hist, ChainArgs{}, nullptr};
+    // psi at the window start = R_{r-1} ... R_0 psi_0; rank 0: bnd[0] = bnd2[0] = hist[0] = psi_0 were written when the grid was allocated
+    if (c->part_rank > 0) {
+        l.win = state_chain(c, c->RX, c->part_rank, 1, c->part_rank, c->psi0, 0, c->wbnd);
+        l.win.pm_bpr = 1; l.win.pm_chunk = (long long)rx_chunk(c);
+        l.win_end = c->wbnd + (size_t)c->part_rank * hstep;
     }
-    ChainArgs s3{};
-    s3.Np = c->Np; s3.cp = c->cp; s3.S = c->nt - 1; s3.Pmat = c->Pc; s3.start = c->bnd;
-    s3.start_stride = (long long)hstep; s3.out = c->hist; s3.nblocks = B; s3.blen = c->scan_blen;
-    s3.ngroups = c->cp / 8;
-    if (guard_is_fused(c)) {
-        s3.guard_diag = c->guard_diag; s3.guard_forcing = c->forcing; s3.scal = c->scal; s3.gN = c->N;
-        s3.gpart = c->gpart_on ? c->gpart : nullptr;
-        s3.n_off = c->n_off; s3.nt_glob = c->nt_glob; s3.count_first = (c->n_off == 0) ? 1 : 0; s3.dt = c->dt; s3.tf = c->tf;
-    }
-    return launch_chain<1>(s3, c->stream);
+    return sweep_levels<1>(c, l);
 }
 
 int qgdk_guard_is_fused(const qgdk_ctx *c) { return guard_is_fused(c) ? 1 : 0; }
@@ -1894,7 +1878,7 @@ int qgdk_terminal_given(const qgdk_ctx *c) { return launch_terminal(c, 1, 1); }
 static int launch_terminal(const qgdk_ctx *c, int write_y, int given_ab)
 {
     const size_t hstep = (size_t)c->Np * 2 * c->cp;
-    double *slot = c->phiRX + (size_t)c->part_rank * phirx_chunk(c) + hstep;     // y_N for the other ranks
+    const YNDest y = yN_dest(c);
     if (hstep >= 32768) {
         // large panels (config 5: 131072 elements): one workgroup took 177 us; many workgroups, two launches
         const int nwg = (int)((hstep + 2047) / 2048);
@@ -1906,19 +1890,17 @@ static int launch_terminal(const qgdk_ctx *c, int write_y, int given_ab)
                                                    (c->gpart_on && c->gpart_terminal && c->have_guard) ? c->gpart : nullptr, c->gpart_n);
             else if (c->gpart_on && c->gpart_terminal && c->have_guard)      // no target: only the guard penalty is to be added up
                 hipLaunchKernelGGL(k_terminal, dim3(1), dim3(256), 0, c->stream, c->hist, c->target, c->forcing, c->yhist, c->scal, c->Np, c->cp, c->nt,
-                                   c->n_ess, 0, 0, slot, slot, slot, 0, c->gpart, c->gpart_n, (const double *)nullptr);
+                                   c->n_ess, 0, 0, y.slot, y.slot, y.slot, 0, c->gpart, c->gpart_n, (const double *)nullptr);
         }
         if (write_y)
             hipLaunchKernelGGL(k_terminal_y, dim3(nwg), dim3(256), 0, c->stream, c->target, c->forcing + (size_t)(c->nt - 1) * hstep,
-                               c->scal, c->yhist + (size_t)(c->nt - 1) * hstep, slot, c->bndY + (size_t)c->scan_blocks * hstep,
-                               c->bndY2 + (size_t)c->scan_blocks2 * hstep, (int)hstep, 2 * c->cp, c->n_ess, c->cost_type, w);
+                               c->scal, y.yhist, y.slot, y.bnd, y.bnd2, (int)hstep, 2 * c->cp, c->n_ess, c->cost_type, w);
         return (int)hipGetLastError();
     }
     // (fused front: the terminal value is lambda_N, formed from termU = L_N^-H target and h_N, into lambda's history)
     hipLaunchKernelGGL(k_terminal, dim3(1), dim3(hstep >= 32768 ? 1024 : 256), 0, c->stream, c->hist, c->target, c->front ? c->hforc : c->forcing,
                        c->front ? c->lam : c->yhist,
-                       c->scal, c->Np, c->cp, c->nt, c->n_ess, c->have_target * (1 + c->cost_type), write_y, slot,
-                       c->bndY + (size_t)c->scan_blocks * hstep, c->bndY2 + (size_t)c->scan_blocks2 * hstep, given_ab,
+                       c->scal, c->Np, c->cp, c->nt, c->n_ess, c->have_target * (1 + c->cost_type), write_y, y.slot, y.bnd, y.bnd2, given_ab,
                        (c->gpart_on && c->gpart_terminal && c->have_guard && !given_ab) ? c->gpart : nullptr, c->gpart_n,
                        c->front ? c->termU : (const double *)nullptr);
     return (int)hipGetLastError();
@@ -1931,35 +1913,39 @@ int qgdk_adjoint_blocks(const qgdk_ctx *c)
     const int B = c->scan_blocks, B2 = c->scan_blocks2, g = c->scan_g;
     const double *PiRx = c->PiX + (size_t)B * pl2;       // panel copies of the block propagators
     int rc;
-    ChainArgs a{};
-    a.Np = c->Np; a.cp = c->cp; a.S = c->nt - 1; a.Pmat = c->Pr; a.forcing = c->front ? c->hforc : c->forcing; a.phi = c->phiX;
-    a.nblocks = B; a.blen = c->scan_blen; a.ngroups = c->cp / 8;
+    ChainArgs a = chain_args(c, c->Pr, c->nt - 1, B, c->scan_blen, c->cp / 8);
+    a.forcing = c->front ? c->hforc : c->forcing; a.phi = c->phiX;
     if (c->fuse_terminal && chain_is_fast(c)) {          // y_N and the overlaps by an extra workgroup of this launch
-        const size_t hstep = (size_t)c->Np * 2 * c->cp;
+        const YNDest y = yN_dest(c);
         a.t_on = 1; a.t_nt = c->nt; a.t_ness = c->n_ess; a.t_have_target = c->have_target * (1 + c->cost_type);
         a.t_hist = c->hist; a.t_target = c->target; a.t_forcing = c->forcing; a.t_yhist = c->yhist; a.t_scal = c->scal;
         if (c->front) { a.t_forcing = c->hforc; a.t_yhist = c->lam; a.t_ytarget = c->termU; }      // fused front: lambda_N itself, into lambda's history
         a.t_gpart = (c->gpart_on && c->gpart_terminal && c->have_guard) ? c->gpart : nullptr; a.t_gpart_n = c->gpart_n;
-        a.t_y2 = c->phiRX + (size_t)c->part_rank * phirx_chunk(c) + hstep;
-        a.t_y3 = c->bndY + (size_t)c->scan_blocks * hstep; a.t_y4 = c->bndY2 + (size_t)c->scan_blocks2 * hstep;
+        a.t_y2 = y.slot; a.t_y3 = y.bnd; a.t_y4 = y.bnd2;
     }
     if ((rc = launch_chain<2>(a, c->stream))) return rc;
     if (B2 > 1) {      // affine parts of the super-blocks (their propagators PiR2 come from the forward sweep)
-        ChainArgs a2{};
-        a2.Np = c->Np; a2.cp = c->cp; a2.S = B; a2.Pmat = PiRx; a2.forcing = c->phiX; a2.phi = c->phi2;
-        a2.nblocks = B2; a2.blen = g; a2.ngroups = c->cp / 8;
+        ChainArgs a2 = chain_args(c, PiRx, B, B2, g, c->cp / 8);
+        a2.forcing = c->phiX; a2.phi = c->phi2;
         if (suffix_on(c)) { a2.mid_out = c->SufPhi; a2.mid_n = g - 2; }      // running affine parts: the suffix sums of the history pass
         if ((rc = launch_chain<2>(a2, c->stream))) return rc;
     }
-    if (c->part_world > 1) {   // affine part of the whole window, into this rank's chunk of phiRX
-        ChainArgs r{};
-        r.Np = c->Np; r.cp = c->cp; r.ngroups = c->cp / 8; r.nblocks = 1;
-        if (B2 > 1) { r.S = B2; r.blen = B2; r.Pmat = c->PiR2; r.forcing = c->phi2; }
-        else { r.S = B; r.blen = B; r.Pmat = PiRx; r.forcing = c->phiX; }
-        r.phi = c->phiRX + (size_t)c->part_rank * phirx_chunk(c);
+    if (c->part_world > 1) {   // affine part of the whole window (of the super-blocks where there are some), into this rank's chunk of phiRX
+        const int n = (B2 > 1) ? B2 : B;
+        ChainArgs r = chain_args(c, (B2 > 1) ? c->PiR2 : PiRx, n, 1, n, c->cp / 8);
+        r.forcing = (B2 > 1) ? c->phi2 : c->phiX; r.phi = c->phiRX + (size_t)c->part_rank * phirx_chunk(c);
         if ((rc = launch_chain<2>(r, c->stream))) return rc;
     }
     return 0;   // the last rank's k_terminal wrote y_N into its second slot of phiRX (and into bndY/bndY2/yhist)
+}
+
+// y_N from src to every place the adjoint scan starts from (yN_dest; src may be one of them)
+int qgdk_copy_yN_to_starts(const qgdk_ctx *c, const double *src)
+{
+    const YNDest y = yN_dest(c);
+    for (double *dst : {y.yhist, y.slot, y.bnd, y.bnd2})
+        if (dst != src) HIPCHK(hipMemcpyAsync(dst, src, (size_t)c->Np * 2 * c->cp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return 0;
 }
 
 // y_N = L(t_N)^H lambda_N for a caller-given terminal lambda (eval_adjoint): one adjoint chain step with
@@ -1967,18 +1953,11 @@ int qgdk_adjoint_blocks(const qgdk_ctx *c)
 int qgdk_apply_LH(const qgdk_ctx *c)
 {
     const size_t hstep = (size_t)c->Np * 2 * c->cp, panel = (size_t)c->Np * 2 * c->Np;
-    ChainArgs a{};
-    a.Np = c->Np; a.cp = c->cp; a.S = 1; a.Pmat = c->L + (size_t)(c->nt - 1) * panel;
-    a.start = c->lam + (size_t)(c->nt - 1) * hstep; a.start_stride = 0; a.out = c->yhist + (size_t)(c->nt - 1) * hstep;
-    a.forcing = c->zero_panel; a.nblocks = 1; a.blen = 1; a.ngroups = c->cp / 8;
-    int rc = launch_chain<3>(a, c->stream);
-    if (rc) return rc;
-    const double *yN = c->yhist + (size_t)(c->nt - 1) * hstep;
-    double *slot = c->phiRX + (size_t)c->part_rank * phirx_chunk(c) + hstep;
-    HIPCHK(hipMemcpyAsync(slot, yN, hstep * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->bndY + (size_t)c->scan_blocks * hstep, yN, hstep * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->bndY2 + (size_t)c->scan_blocks2 * hstep, yN, hstep * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    return 0;
+    double *yN = yN_dest(c).yhist;
+    ChainArgs a = state_chain(c, c->L + (size_t)(c->nt - 1) * panel, 1, 1, 1, c->lam + (size_t)(c->nt - 1) * hstep, 0, yN);
+    a.forcing = c->zero_panel;
+    const int rc = launch_chain<3>(a, c->stream);
+    return rc ? rc : qgdk_copy_yN_to_starts(c, yN);
 }
 
 // adjoint, part 2 (after the all-gather of phiRX): y at the window end, at the super-block and block
@@ -1988,20 +1967,19 @@ int qgdk_adjoint_finish(const qgdk_ctx *c)
     const size_t hstep = (size_t)c->Np * 2 * c->cp, pl2 = (size_t)2 * c->Np * c->Np;
     const int B = c->scan_blocks, B2 = c->scan_blocks2, g = c->scan_g, W = c->part_world, r = c->part_rank;
     const double *PiRx = c->PiX + (size_t)B * pl2;
-    int rc;
+    double *yN = yN_dest(c).yhist;                                                           // y at this rank's end of the grid
+    const double *yN_last = c->phiRX + (size_t)(W - 1) * phirx_chunk(c) + hstep;             // y_N as the last rank sent it
     if (chain_is_fast(c)) {
         // one launch, mirror image of the forward one: y_N is advanced over the windows of the higher ranks,
         // the super-blocks and the blocks after b, then the block writes its y history
-        ChainArgs s3{};
-        s3.Np = c->Np; s3.cp = c->cp; s3.S = c->nt - 1; s3.Pmat = c->Pr; s3.forcing = c->forcing; s3.out = c->yhist;
-        s3.nblocks = B; s3.blen = c->scan_blen; s3.ngroups = c->cp / 8; s3.start_stride = 0;
-        s3.start = (r == W - 1) ? c->yhist + (size_t)(c->nt - 1) * hstep : c->phiRX + (size_t)(W - 1) * phirx_chunk(c) + hstep;
+        ChainArgs s3 = state_chain(c, c->Pr, c->nt - 1, B, c->scan_blen, (r == W - 1) ? yN : yN_last, 0, c->yhist);
+        s3.forcing = c->forcing;
         if (c->front) { s3.forcing = c->hforc; s3.out = c->lam; s3.start = c->lam + (size_t)(c->nt - 1) * hstep; }      // fused front: the sweep is in lambda
         int q = 0;
         if (r < W - 1) {
             s3.pre_kind[q] = 0; s3.pre_P[q] = c->RX + (size_t)(r + 1) * rx_chunk(c) + pl2; s3.pre_pm_bpr[q] = 1;
             s3.pre_pm_chunk[q] = (long long)rx_chunk(c); s3.pre_f[q] = c->phiRX + (size_t)(r + 1) * phirx_chunk(c); s3.pre_f_bpr[q] = 1;
-            s3.pre_rank_count = W - 1 - r; s3.pre_start_out = c->yhist + (size_t)(c->nt - 1) * hstep; q++;
+            s3.pre_rank_count = W - 1 - r; s3.pre_start_out = yN; q++;
         }
         if (B2 > 1) { s3.pre_kind[q] = 1; s3.pre_P[q] = c->PiR2; s3.pre_f[q] = c->phi2; q++; }
         if (B > 1) { s3.pre_kind[q] = 2; s3.pre_P[q] = PiRx; s3.pre_f[q] = c->phiX; q++; }
@@ -2009,41 +1987,14 @@ int qgdk_adjoint_finish(const qgdk_ctx *c)
         if (suffix_on(c)) { s3.suf_P = c->SufP; s3.suf_phi = c->SufPhi; s3.suf_n = g - 2; }
         return launch_chain<3>(s3, c->stream);
     }
+    SweepLevels l{c->PiR2, PiRx, c->Pr, c->phi2, c->phiX, c->forcing, c->bndY2, c->bndY, c->yhist, ChainArgs{}, nullptr};
     if (r < W - 1) {   // y at the window end: y <- R_q^H y + phi^rank_q for q = W-1 .. r+1, from y_N
-        const int nq = W - 1 - r;
-        ChainArgs w{};
-        w.Np = c->Np; w.cp = c->cp; w.S = nq; w.nblocks = 1; w.blen = nq; w.ngroups = c->cp / 8;
-        w.Pmat = c->RX + (size_t)(r + 1) * rx_chunk(c) + pl2; w.pm_bpr = 1; w.pm_chunk = (long long)rx_chunk(c);
-        w.forcing = c->phiRX + (size_t)(r + 1) * phirx_chunk(c); w.f_bpr = 1;       // slot of q is 2q: [phi | y_N] per rank
-        w.start = c->phiRX + (size_t)(W - 1) * phirx_chunk(c) + hstep; w.start_stride = 0; w.out = c->wbndY;
-        if ((rc = launch_chain<3>(w, c->stream))) return rc;
-        // out[q'] = y before window r+1+q': y at the end of this rank's window is out[0]
-        HIPCHK(hipMemcpyAsync(c->bndY + (size_t)B * hstep, c->wbndY, hstep * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->bndY2 + (size_t)B2 * hstep, c->wbndY, hstep * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->yhist + (size_t)(c->nt - 1) * hstep, c->wbndY, hstep * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        l.win = state_chain(c, c->RX + (size_t)(r + 1) * rx_chunk(c) + pl2, W - 1 - r, 1, W - 1 - r, yN_last, 0, c->wbndY);
+        l.win.pm_bpr = 1; l.win.pm_chunk = (long long)rx_chunk(c);
+        l.win.forcing = c->phiRX + (size_t)(r + 1) * phirx_chunk(c); l.win.f_bpr = 1;       // slot of q is 2q: [phi | y_N] per rank
+        l.win_end = c->wbndY;      // out[q'] = y before window r+1+q': y at the end of this rank's window is out[0]
     }
-    if (B2 <= 1) {
-        ChainArgs s2{};
-        s2.Np = c->Np; s2.cp = c->cp; s2.S = B; s2.Pmat = PiRx;
-        s2.start = c->bndY + (size_t)B * hstep; s2.start_stride = 0; s2.out = c->bndY;
-        s2.forcing = c->phiX; s2.nblocks = 1; s2.blen = B; s2.ngroups = c->cp / 8;
-        if ((rc = launch_chain<3>(s2, c->stream))) return rc;
-    } else {
-        ChainArgs b2{};   // y at super-block starts
-        b2.Np = c->Np; b2.cp = c->cp; b2.S = B2; b2.Pmat = c->PiR2; b2.start = c->bndY2 + (size_t)B2 * hstep; b2.start_stride = 0;
-        b2.out = c->bndY2; b2.forcing = c->phi2; b2.nblocks = 1; b2.blen = B2; b2.ngroups = c->cp / 8;
-        if ((rc = launch_chain<3>(b2, c->stream))) return rc;
-        ChainArgs c2{};   // y at every block start
-        c2.Np = c->Np; c2.cp = c->cp; c2.S = B; c2.Pmat = PiRx;
-        c2.start = c->bndY2 + hstep; c2.start_stride = (long long)hstep; c2.out = c->bndY; c2.forcing = c->phiX;
-        c2.nblocks = B2; c2.blen = g; c2.ngroups = c->cp / 8;
-        if ((rc = launch_chain<3>(c2, c->stream))) return rc;
-    }
-    ChainArgs s3{};
-    s3.Np = c->Np; s3.cp = c->cp; s3.S = c->nt - 1; s3.Pmat = c->Pr; s3.start = c->bndY + hstep;
-    s3.start_stride = (long long)hstep; s3.out = c->yhist; s3.forcing = c->forcing; s3.nblocks = B;
-    s3.blen = c->scan_blen; s3.ngroups = c->cp / 8;
-    return launch_chain<3>(s3, c->stream);
+    return sweep_levels<3>(c, l);
 }
 
 // Sensitivities of all control parameters at once (forced gradient): column group = (parameter, state
@@ -2054,22 +2005,19 @@ int qgdk_forced_chains(const qgdk_ctx *c)
 {
     const int cpS = c->n_pcof * c->cp, B = c->scan_blocks;
     const size_t hstepS = (size_t)c->Np * 2 * cpS;
-    ChainArgs f{};
-    f.Np = c->Np; f.cp = cpS; f.fs_mode = 1; f.fs_m = c->m; f.fs_nops = c->n_ops; f.fs_gpc = c->cp / 8; f.fs_nt = c->g_nt ? c->g_nt : c->nt; f.fs_n0 = c->g_n0;
+    ChainArgs f = chain_args(c, c->Pc, c->nt - 1, B, c->scan_blen, cpS / 8);      // the launches over the steps: (i) and (iii)
+    f.cp = cpS; f.fs_mode = 1; f.fs_m = c->m; f.fs_nops = c->n_ops; f.fs_gpc = c->cp / 8; f.fs_nt = c->g_nt ? c->g_nt : c->nt; f.fs_n0 = c->g_n0;
     f.fs_BR = c->fs_BR; f.fs_BL = c->fs_BL; f.fs_G = c->G; f.fs_goff = c->goff; f.fs_ncoef = c->ncoef; f.fs_poff = c->poff;
     ChainArgs a = f;   // (i)
-    a.S = c->nt - 1; a.Pmat = c->Pc; a.phi = c->fs_phi; a.nblocks = B; a.blen = c->scan_blen; a.ngroups = cpS / 8;
+    a.phi = c->fs_phi;
     int rc = launch_chain<4>(a, c->stream);
     if (rc) return rc;
-    ChainArgs s2{};    // (ii)
-    s2.Np = c->Np; s2.cp = cpS; s2.S = B; s2.Pmat = c->PiX;
-    s2.start = c->fs_bnd; s2.start_stride = 0; s2.out = c->fs_bnd; s2.forcing = c->fs_phi; s2.nblocks = 1; s2.blen = B;
-    s2.ngroups = cpS / 8; s2.fs_gpc = c->cp / 8;
+    ChainArgs s2 = state_chain(c, c->PiX, B, 1, B, c->fs_bnd, 0, c->fs_bnd);    // (ii)
+    s2.cp = cpS; s2.ngroups = cpS / 8; s2.forcing = c->fs_phi; s2.fs_gpc = c->cp / 8;
     if ((rc = launch_chain<5>(s2, c->stream))) return rc;
     if (c->have_guard || c->fs_shist) {   // (iii); fs_shist: every s_n is also stored (the exact Hessian)
         ChainArgs g = f;
-        g.S = c->nt - 1; g.Pmat = c->Pc; g.start = c->fs_bnd; g.start_stride = (long long)hstepS; g.nblocks = B; g.blen = c->scan_blen;
-        g.ngroups = cpS / 8; g.out = c->fs_shist;
+        g.start = c->fs_bnd; g.start_stride = (long long)hstepS; g.out = c->fs_shist;
         if (c->have_guard) { g.fs_gf = c->forcing; g.fs_gacc = c->fs_gacc; }
         if ((rc = launch_chain<5>(g, c->stream))) return rc;
     }
@@ -2083,18 +2031,15 @@ int qgdk_forcing_sweep(const qgdk_ctx *c)
     const size_t hstep = (size_t)c->Np * 2 * c->cp;
     const int B = c->scan_blocks;
     int rc;
-    ChainArgs a{};     // affine parts from zero
-    a.Np = c->Np; a.cp = c->cp; a.S = c->nt - 1; a.Pmat = c->Pc; a.forcing = c->ff_Q; a.phi = c->ff_phi;
-    a.nblocks = B; a.blen = c->scan_blen; a.ngroups = c->cp / 8;
+    ChainArgs a = chain_args(c, c->Pc, c->nt - 1, B, c->scan_blen, c->cp / 8);     // affine parts from zero
+    a.forcing = c->ff_Q; a.phi = c->ff_phi;
     if ((rc = launch_chain<4>(a, c->stream))) return rc;
     HIPCHK(hipMemcpyAsync(c->ff_bnd, c->psi0, hstep * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    ChainArgs s2{};    // states at the block boundaries
-    s2.Np = c->Np; s2.cp = c->cp; s2.S = B; s2.Pmat = c->PiX; s2.start = c->ff_bnd; s2.start_stride = 0; s2.out = c->ff_bnd;
-    s2.forcing = c->ff_phi; s2.nblocks = 1; s2.blen = B; s2.ngroups = c->cp / 8;
+    ChainArgs s2 = state_chain(c, c->PiX, B, 1, B, c->ff_bnd, 0, c->ff_bnd);       // states at the block boundaries
+    s2.forcing = c->ff_phi;
     if ((rc = launch_chain<5>(s2, c->stream))) return rc;
-    ChainArgs s3{};    // history
-    s3.Np = c->Np; s3.cp = c->cp; s3.S = c->nt - 1; s3.Pmat = c->Pc; s3.start = c->ff_bnd; s3.start_stride = (long long)hstep;
-    s3.out = c->hist; s3.forcing = c->ff_Q; s3.nblocks = B; s3.blen = c->scan_blen; s3.ngroups = c->cp / 8;
+    ChainArgs s3 = state_chain(c, c->Pc, c->nt - 1, B, c->scan_blen, c->ff_bnd, hstep, c->hist);      // history
+    s3.forcing = c->ff_Q;
     return launch_chain<5>(s3, c->stream);
 }
 
@@ -2112,12 +2057,9 @@ int qgdk_lambda(const qgdk_ctx *c)
     if (c->dense_gemm && !c->use_sparse && c->nt > 1) return qgdk_dense_lambda(c);
 #define CALL_LC(N) hipLaunchKernelGGL((k_lambda_c<N>), dim3(c->cp / 8, c->nt - 1), dim3(256), 0, c->stream, c->LinvT, c->yhist, c->lam, \
                                       c->cp, c->sigma, c->nt * c->n_ops * c->m * 2, c->grad, c->grad_accumulate ? 0 : c->n_pcof)
-    if (c->nt > 1) switch (c->Np) {
-        case 16: CALL_LC(16); return (int)hipGetLastError();
-        case 32: CALL_LC(32); return (int)hipGetLastError();
-        case 48: CALL_LC(48); return (int)hipGetLastError();
-        case 64: CALL_LC(64); return (int)hipGetLastError();
-        default: break;
+    if (c->nt > 1 && qgdk_np_compiled(c->Np)) {
+        DISPATCH_NP(c->Np, CALL_LC)
+        return (int)hipGetLastError();
     }
 #undef CALL_LC
     size_t shm = (size_t)c->Np * 16 * sizeof(double);

@@ -181,15 +181,11 @@ int qgdk_hvp_forcing(const qgdk_ctx *c, const double *Z, const double *half, con
 }
 
 // mu: the adjoint sweep of `a` (a context copy whose forcing / yhist / lam are the product's own buffers) from the terminal
-// value y_N = forcing[nt-1], copied to every place the adjoint scan starts from (as qgdk_apply_LH does)
+// value y_N = forcing[nt-1], copied to every place the adjoint scan starts from
 int qgdk_hvp_adjoint(const qgdk_ctx *a)
 {
-    const size_t hstep = (size_t)a->Np * 2 * a->cp;
-    const double *yN = a->forcing + (size_t)(a->nt - 1) * hstep;
-    for (double *dst : {a->yhist + (size_t)(a->nt - 1) * hstep, a->phiRX + hstep, a->bndY + (size_t)a->scan_blocks * hstep,
-                        a->bndY2 + (size_t)a->scan_blocks2 * hstep})
-        HIPCHK(hipMemcpyAsync(dst, yN, hstep * sizeof(double), hipMemcpyDeviceToDevice, a->stream));
     int rc;
+    if ((rc = qgdk_copy_yN_to_starts(a, a->forcing + (size_t)(a->nt - 1) * a->Np * 2 * a->cp))) return rc;
     if ((rc = qgdk_adjoint_blocks(a)) || (rc = qgdk_adjoint_finish(a))) return rc;
     return qgdk_lambda(a);
 }

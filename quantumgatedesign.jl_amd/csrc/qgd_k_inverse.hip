@@ -1170,17 +1170,16 @@ int qgdk_inverse(const qgdk_ctx *c)
 {
     const int nmat = c->nt - 1;
     if (nmat <= 0) return 0;
-    switch (c->Np) {     // Np <= 64: inverse and propagator in one launch, the matrix in registers
-#define CALL_IMF(N) case N: hipLaunchKernelGGL((k_inverse_mfma<N>), dim3(nmat), dim3(N * 4), 0, c->stream, c->L, c->R, c->LinvT, c->Pr, c->Pc, 1, c->status); \
-                            return (int)hipGetLastError()
-        CALL_IMF(16); CALL_IMF(32); CALL_IMF(48);
+    // Np <= 64: inverse and propagator in one launch, the matrix in registers.  Np = 64: column-block elimination of [L | R]
+    // (qgd_inverse_cb.h); QGD_PATHS=inv_panels: its last resort, the 4-pivot panel kernel, for every matrix
+#define CALL_IMF(N) do { hipLaunchKernelGGL((k_inverse_mfma<N>), dim3(nmat), dim3(N * 4), 0, c->stream, c->L, c->R, c->LinvT, c->Pr, c->Pc, 1, c->status); \
+                         return (int)hipGetLastError(); } while (0)
+    if (c->Np != 64 || qgd_path("inv_panels")) DISPATCH_NP(c->Np, CALL_IMF)
 #undef CALL_IMF
-    case 64:   // column-block elimination of [L | R] (qgd_inverse_cb.h); QGD_PATHS=inv_panels: its last resort, the 4-pivot panel kernel, for every matrix
-        if (qgd_path("inv_panels")) hipLaunchKernelGGL((k_inverse_mfma<64>), dim3(nmat), dim3(256), 0, c->stream, c->L, c->R, c->LinvT, c->Pr, c->Pc, 1, c->status);
-        else if (nmat > CB_ONE_ALONE && nmat <= CB_ONE_ROUND) hipLaunchKernelGGL(k_inverse_cb<true>, dim3(nmat), dim3(256), 0, c->stream, c->L, c->R, c->LinvT, c->Pr, c->Pc, 1, c->status, c->status + 1);
+    if (c->Np == 64) {
+        if (nmat > CB_ONE_ALONE && nmat <= CB_ONE_ROUND) hipLaunchKernelGGL(k_inverse_cb<true>, dim3(nmat), dim3(256), 0, c->stream, c->L, c->R, c->LinvT, c->Pr, c->Pc, 1, c->status, c->status + 1);
         else hipLaunchKernelGGL(k_inverse_cb<false>, dim3(nmat), dim3(256), 0, c->stream, c->L, c->R, c->LinvT, c->Pr, c->Pc, 1, c->status, c->status + 1);
         return (int)hipGetLastError();
-    default: break;
     }
     if (c->Np > 64 && c->dense_gemm) {    // (any size: no LDS limit)
         const int took = qgdk_dense_inverse(c);              // block Gauss-Jordan as batched GEMM launches (qgd_k_dense.hip)
@@ -1219,12 +1218,10 @@ int qgdk_inverse(const qgdk_ctx *c)
 int qgdk_inverse_diag(const qgdk_ctx *c, const double *Win, size_t mstride, int ldw, size_t off, int bs, double *DkC, int *flags)
 {
     const int nmat = c->nt - 1;
-    switch (bs) {
-#define CALL_ID(N) case N: hipLaunchKernelGGL((k_inverse_diag<N>), dim3(nmat), dim3(N * 4), 0, c->stream, Win, mstride, ldw, off, DkC, 1, flags); break
-        CALL_ID(16); CALL_ID(32); CALL_ID(48); CALL_ID(64);
+    if (!qgdk_np_compiled(bs)) return -1;
+#define CALL_ID(N) hipLaunchKernelGGL((k_inverse_diag<N>), dim3(nmat), dim3(N * 4), 0, c->stream, Win, mstride, ldw, off, DkC, 1, flags)
+    DISPATCH_NP(bs, CALL_ID)
 #undef CALL_ID
-    default: return -1;
-    }
     return (int)hipGetLastError();
 }
 
@@ -1250,7 +1247,7 @@ int qgdk_inverse_redo(const qgdk_ctx *c, const int *flags)
     return (int)hipGetLastError();
 }
 
-int qgdk_propagator_is_fused(const qgdk_ctx *c) { return c->Np == 16 || c->Np == 32 || c->Np == 48 || c->Np == 64; }
+int qgdk_propagator_is_fused(const qgdk_ctx *c) { return qgdk_np_compiled(c->Np); }
 
 int qgdk_propagator(const qgdk_ctx *c)
 {

@@ -183,3 +183,8 @@ __device__ __forceinline__ void combine_opvals(const OpVals &v, const double *cf
 #define DISPATCH_NOPS(n_ops, CALL) \
     switch (n_ops) { case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; \
                      default: CALL(-1); break; }
+
+// CALL(N) for the compiled sizes of Np (qgdk_np_compiled), nothing for any other
+#define DISPATCH_NP(Np, CALL) \
+    switch (Np) { case 16: CALL(16); break; case 32: CALL(32); break; case 48: CALL(48); break; case 64: CALL(64); break; \
+                  default: break; }

@@ -11,7 +11,7 @@ SRC=$ROOT/quantumgatedesign.jl_amd/csrc
 OUT=$ROOT/scripts/ubench/bin
 B=$OUT/_build_$NAME
 mkdir -p $B
-for k in qgd_k_build qgd_k_inverse qgd_k_chain qgd_k_grad qgd_k_sparse qgd_k_forced qgd_k_dense qgd_k_layout qgd_k_tiny; do
+for k in qgd_k_build qgd_k_inverse qgd_k_chain qgd_k_grad qgd_k_sparse qgd_k_forced qgd_k_dense qgd_k_layout qgd_k_tiny qgd_k_hessian qgd_k_hvp qgd_k_observe; do
   F="$FLAGS"; if [ -n "$ONLY" ] && ! echo " $ONLY " | grep -q " $k "; then F=""; fi
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function $F -I$SRC -I$ROOT/include -c $SRC/$k.hip -o $B/$k.o &
 done
