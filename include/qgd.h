@@ -418,6 +418,32 @@ int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *h
  * n_vec vectors give what n_vec single calls give.  DESIGN.md section 4d. */
 int qgd_eval_hessian_vec(qgd_handle h, const double *pcof, int32_t n_pcof, const double *v, int32_t n_vec, double *hv, double *grad);
 
+/* Pullback of the trajectory outputs to pcof: grad[n_pcof] = sum over the parts given of <bar, d output / d pcof>, the
+ * gradient of any cost a caller writes in terms of the outputs of qgd_eval_states, qgd_eval_populations and
+ * qgd_eval_expectations, with bar = d cost / d output.  states_bar [2N, n_slots, n_cols], pop_bar [N, n_slots, n_cols] (or
+ * [n_groups, ..] with level_map [n_groups x N] column-major) and expect_bar [n_obs, n_slots, n_cols] with the observables'
+ * planes obs_re, obs_im [N, N, n_obs] (obs_im NULL: real observables) have the shapes and layouts of those outputs,
+ * qgd_set_save_every included (n_slots = 1 + nsteps / s: a slot addresses time point k * s, the other time points carry no
+ * cotangent); each of the three is nullable.  Slot 0 is ignored: the initial state does not depend on pcof.  No weights are
+ * applied -- the caller's cotangent is the whole weight.  One forward sweep on the general two-point path (a small problem
+ * takes it too), the stage derivatives, the forcing kernel (qgd_k_pullback.hip), one adjoint sweep with that forcing and one
+ * gradient contraction.  history_precomputed under the rule of qgd_discrete_adjoint.  pcof may be NULL when tables and basis
+ * were set directly (the basis is then the Jacobian at the current pcof).  No target is needed.
+ *   The adjoint sweep runs in buffers of its own (kept on the handle): lambda, the guard forcing and the scalars of the stored
+ * evaluation stay as they are, the stored sweep is left as qgd_eval_forward without an output array leaves it, with the stage
+ * derivatives formed, and the kept setup of qgd_eval_hessian_vec stays valid when the sweep is reused (no buffer is shared with
+ * it; a sweep that is redone voids it as every forward sweep does).  Deterministic: the same bits on every run.
+ * Refusals, before anything is launched.  QGD_ERR_ARGUMENT: all three cotangents NULL, NULL grad, level_map given with
+ * n_groups < 1, expect_bar without obs_re or with n_obs < 1, a pcof of another length.  QGD_ERR_STATE: no control basis, a
+ * partitioned handle or one with a communicator, history_precomputed without a previous forward evaluation.
+ * QGD_ERR_UNSUPPORTED: a windowed time grid, N > 64, no control operators.  QGD_ERR_MEMORY when the three panel histories and
+ * the uploaded cotangents do not fit the memory budget or the free device memory.  DESIGN.md section 4g. */
+int qgd_eval_pullback(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
+                      const double *states_bar,
+                      const double *pop_bar, const double *level_map, int32_t n_groups,
+                      const double *expect_bar, const double *obs_re, const double *obs_im, int32_t n_obs,
+                      double *grad);
+
 /* Operator path of the step-matrix and gradient kernels.  mode 0: automatic (sparse when every
  * row of the assembled Hamiltonian has at most min(16, N/2) entries and N <= 64 -- the drift +
  * a_k +/- a_k^dagger operators of src/multi_qudit_systems.jl -- else dense), 1: dense fp64 MFMA

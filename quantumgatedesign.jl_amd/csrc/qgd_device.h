@@ -212,6 +212,11 @@ int qgdk_hvp_forcing(const qgdk_ctx *c, const double *Z, const double *half, con
                      const double *gvt, const double *term, double *F, double *part);
 int qgdk_hvp_adjoint(const qgdk_ctx *a);
 int qgdk_hvp_contract(const qgdk_ctx *c, const double *part, const double *gB, double *out);
+/* qgd_k_pullback.hip: F [nt][Np][2cp] = -f, the adjoint scan's forcing (and, in its last panel, terminal value) of the
+   cotangents of the three trajectory outputs (device arrays in the outputs' layouts, slot k at time point k * save; each of
+   sbar, pbar, ebar may be null); every panel is written */
+int qgdk_pullback_forcing(const qgdk_ctx *c, double *F, int save, const double *sbar, const double *pbar, const double *map_dev,
+                          int n_groups, const double *ebar, const double *obs_re, const double *obs_im, int n_obs);
 int qgdk_forcing_terms(const qgdk_ctx *c);
 int qgdk_forcing_add_derivs(const qgdk_ctx *c);
 int qgdk_forcing_sweep(const qgdk_ctx *c);

@@ -2,7 +2,7 @@
 // launch macros, the phase timer and the internal entry points of each unit.
 //   qgd_host_alloc.cpp    handles: creation, validation (SchrodingerProb.jl:73-154), the time grid and its windows, setters
 //   qgd_host_eval.cpp     one evaluation: forward / adjoint phases, result transport, the evaluation entry points
-//   qgd_host_sens.cpp     sensitivities of the state to the parameters: the forced gradient, the exact Hessian, Hessian-vector products
+//   qgd_host_sens.cpp     sensitivities of the state to the parameters: the forced gradient, the exact Hessian, Hessian-vector products, pullbacks
 //   qgd_host_output.cpp   reference-layout output arrays of a resident or windowed grid: the copy stream, staging, the one transport
 //   qgd_host_windows.cpp  time grids in bounded memory: window entry, the windowed forward and adjoint passes
 //   qgd_host_comm.cpp     several GPUs: the RCCL binding, the collective evaluation and its failure mode
@@ -100,6 +100,15 @@ struct qgd_handle_s {
     size_t hvp_key = 0;                // (nt, n_pcof, basis directions, general guard, scan blocks) they were sized for
     bool hvp_valid = false;
     std::vector<double> hvp_grad;      // the adjoint gradient of the setup
+    // qgd_eval_pullback: the forcing, y and mu of its adjoint sweep -- three panel histories of its own,
+    // none shared with the setup above, which a pullback therefore leaves valid -- its gradient and scalars, and the caller's
+    // cotangents, level map and observable planes on the device
+    struct PullbackBufs {
+        double *F = nullptr, *Y = nullptr, *mu = nullptr, *gB = nullptr, *scal = nullptr;
+        double *sbar = nullptr, *pbar = nullptr, *map = nullptr, *ebar = nullptr, *planes = nullptr;
+    } pb;
+    std::vector<void *> pullback_bufs;
+    std::vector<size_t> pullback_key;  // (nt, n_pcof, and the lengths of the five uploads) they were sized for; empty: none
     std::vector<void *> forcing_bufs;  // eval_forward with a user forcing
     double *fsc_forcing = nullptr;     // (in forcing_bufs) the same slab for k_forcing_terms
     size_t forcing_key = 0;

@@ -1,6 +1,7 @@
 // qgd_host_sens.cpp -- host side of the C ABI (include/qgd.h), sensitivities of the state to the parameters: the forced gradient
-// (eval_grad_forced.jl:17-194), the exact Hessian and Hessian-vector products (section 4d).  The three
-// share the forced gradient's buffers, and the two second-order entry points their refusals and their setup.
+// (eval_grad_forced.jl:17-194), the exact Hessian, Hessian-vector products (section 4d) and the pullback of
+// trajectory outputs (section 4g).  The first three share the forced gradient's buffers, and the two second-order entry points
+// their refusals and their setup; the pullback runs the second-order adjoint's sweep with a forcing of the caller's.
 #include "qgd_host.h"
 
 using namespace qgdh;
@@ -31,12 +32,13 @@ static int forced_buffers(qgd_handle h, size_t nt, size_t B, size_t *bytes = nul
 
 
 // The pool of a second-order entry point, anew from its plan.  QGD_ERR_MEMORY is decided from what THIS call allocates: the plan
-// and, when they are not there under the right key, the forced gradient's buffers.
-static int second_order_alloc(qgd_handle h, std::vector<void *> &pool, const std::vector<Buf> &plan, const std::string &what)
+// and, when they are not there under the right key, the forced gradient's buffers (with_forced: the entry point needs them).
+static int second_order_alloc(qgd_handle h, std::vector<void *> &pool, const std::vector<Buf> &plan, const std::string &what,
+                              bool with_forced = true)
 {
     free_pool(pool);
     size_t bytes = plan_bytes(plan), fr = 0, tot = 0;
-    (void)forced_buffers(h, (size_t)h->k.nt, (size_t)h->k.scan_blocks, &bytes);
+    if (with_forced) (void)forced_buffers(h, (size_t)h->k.nt, (size_t)h->k.scan_blocks, &bytes);
     if ((h->mem_budget && bytes > h->mem_budget) || (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr))
         return fail(h, QGD_ERR_MEMORY, what + " (" + std::to_string(bytes) + " bytes needed)");
     return plan_alloc(h, pool, plan);
@@ -226,6 +228,29 @@ static int hvp_terminal(qgd_handle h, const double *svN_dev, double *term_dev)
 }
 
 
+// buffers of qgd_eval_pullback for the present grid and basis and the sizes of this call's uploads (doubles; 0: not given)
+static int pullback_buffers(qgd_handle h, size_t n_sbar, size_t n_pbar, size_t n_map, size_t n_ebar, size_t n_planes)
+{
+    qgdk_ctx &k = h->k;
+    const size_t hist = (size_t)k.nt * k.Np * 2 * k.cp, np = (size_t)k.n_pcof;
+    const std::vector<size_t> key = {(size_t)k.nt, np, n_sbar, n_pbar, n_map, n_ebar, n_planes};
+    if (h->pullback_key == key) return QGD_OK;
+    auto &b = h->pb;
+    h->pullback_key.clear();
+    int rc = second_order_alloc(h, h->pullback_bufs, {
+        {&b.F, hist}, {&b.Y, hist}, {&b.mu, hist}, {&b.gB, np}, {&b.scal, 4}, {&b.sbar, n_sbar, n_sbar != 0}, {&b.pbar, n_pbar, n_pbar != 0},
+        {&b.map, n_map, n_map != 0}, {&b.ebar, n_ebar, n_ebar != 0}, {&b.planes, n_planes, n_planes != 0}},
+        "the buffers of qgd_eval_pullback do not fit", false);
+    if (rc) return rc;
+    // mu_0 and y_0 are never written; the forcing kernel writes every panel of F on every call
+    HIP_TRY(h, hipMemsetAsync(b.mu, 0, hist * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.Y, 0, hist * sizeof(double), k.stream));
+    HIP_TRY(h, hipMemsetAsync(b.scal, 0, 4 * sizeof(double), k.stream));
+    h->pullback_key = key;
+    return QGD_OK;
+}
+
+
 extern "C" {
 
 int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, double *grad)
@@ -354,6 +379,65 @@ int qgd_eval_hessian_vec(qgd_handle h, const double *pcof, int32_t n_pcof, const
         HIP_TRY(h, hipStreamSynchronize(k.stream));
     }
     if (grad) memcpy(grad, h->hvp_grad.data(), np * sizeof(double));
+    return QGD_OK;
+}
+
+
+
+// pullback of the trajectory outputs to pcof: the forward sweep on the general two-point path (or the
+// stored one), the stage derivatives, k_pullback_forcing, then term (B) of the Hessian-vector product as it stands -- the adjoint
+// sweep with that forcing (mu) and the gradient kernels with mu in place of lambda, on a context copy with buffers of its own.
+int qgd_eval_pullback(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
+                      const double *states_bar,
+                      const double *pop_bar, const double *level_map, int32_t n_groups,
+                      const double *expect_bar, const double *obs_re, const double *obs_im, int32_t n_obs,
+                      double *grad)
+{
+    if (h) drop_graph(h);
+    if (!h || !grad) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    if (!states_bar && !pop_bar && !expect_bar) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_pullback needs at least one of states_bar, pop_bar, expect_bar");
+    if (level_map && n_groups < 1) return fail(h, QGD_ERR_ARGUMENT, "a level map needs n_groups >= 1");
+    if (expect_bar && (!obs_re || n_obs < 1)) return fail(h, QGD_ERR_ARGUMENT, "expect_bar needs obs_re and n_obs >= 1");
+    HIP_TRY(h, hipSetDevice(h->device));
+    NEED_GRID(h);
+    qgdk_ctx &k = h->k;
+    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_eval_pullback");
+    if (h->part_world != 1 || h->comm) return fail(h, QGD_ERR_STATE, "partitioned handle: the pullback is single-GPU");
+    if (pcof && n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
+    if (h->chunks_eff > 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_pullback needs the whole time grid resident (this handle processes it in windows)");
+    if (k.N > 64) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_pullback supports N <= 64");
+    if (k.n_ops < 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_pullback needs control operators");
+    if (!pcof && !h->have_tables) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
+    if (history_precomputed && h->sweep.kind == SWEEP_NONE)
+        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+    const int save = h->save_every;
+    const size_t np = (size_t)k.n_pcof, N = k.N, sc = (size_t)(1 + (k.nt - 1) / save) * k.c;      // sc: slots x columns
+    const bool with_map = pop_bar && level_map, with_im = expect_bar && obs_im;
+    const size_t n_sbar = states_bar ? 2 * N * sc : 0, n_pbar = pop_bar ? (with_map ? (size_t)n_groups : N) * sc : 0;
+    const size_t n_map = with_map ? (size_t)n_groups * N : 0, n_ebar = expect_bar ? (size_t)n_obs * sc : 0;
+    const size_t n_plane = expect_bar ? (size_t)n_obs * N * N : 0;
+    int rc;
+    if ((rc = pullback_buffers(h, n_sbar, n_pbar, n_map, n_ebar, (with_im ? 2 : 1) * n_plane))) return rc;
+    const auto &b = h->pb;
+    const struct { double *dst; const double *src; size_t n; } up[] = {
+        {b.sbar, states_bar, n_sbar}, {b.pbar, pop_bar, n_pbar}, {b.map, level_map, n_map}, {b.ebar, expect_bar, n_ebar},
+        {b.planes, obs_re, n_plane}, {with_im ? b.planes + n_plane : nullptr, obs_im, with_im ? n_plane : 0}};
+    for (const auto &u : up)
+        if (u.n) HIP_TRY(h, hipMemcpyAsync(u.dst, u.src, u.n * sizeof(double), hipMemcpyHostToDevice, k.stream));
+    if (!(history_precomputed && h->sweep.kind == SWEEP_GENERAL && sweep_reusable(h, pcof, n_pcof)) &&
+        (rc = run_forward(h, pcof, n_pcof))) return rc;
+    if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
+    { PhaseTimer t(h, "pullback_forcing");
+      K_TRY(h, qgdk_pullback_forcing(&k, b.F, save, b.sbar, b.pbar, b.map, n_groups, b.ebar, b.planes, with_im ? b.planes + n_plane : nullptr, n_obs)); }
+    // (as the second-order adjoint of qgd_eval_hessian_vec: lambda, the guard forcing and the scalars of the stored evaluation stay)
+    qgdk_ctx a = k;
+    a.forcing = b.F; a.yhist = b.Y; a.lam = b.mu; a.grad = b.gB; a.scal = b.scal;
+    a.front = 0; a.fuse_terminal = 0; a.grad_accumulate = 0; a.mirror_dev = nullptr; a.mirror_ticket = nullptr;
+    { PhaseTimer t(h, "pullback_adjoint"); K_TRY(h, qgdk_hvp_adjoint(&a)); }
+    { PhaseTimer t(h, "pullback_gradient"); K_TRY(h, qgdk_gradient(&a)); }
+    if ((rc = check_status(h))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(grad, b.gB, np * sizeof(double), hipMemcpyDeviceToHost, k.stream));
+    HIP_TRY(h, hipStreamSynchronize(k.stream));
     return QGD_OK;
 }
 

@@ -11,6 +11,8 @@ behaviour as the reference:
   get_populations(history)                                        state_vector_helpers.jl:10-52
   eval_populations(prob, controls, pcof; order, saveEveryNsteps, level_map)   the same populations, formed on the device
   eval_expectations(prob, controls, pcof, observables; order, saveEveryNsteps)   Re(psi^H O psi) along the sweep, on the device
+  eval_pullback(prob, controls, pcof; order, saveEveryNsteps, states_bar, populations_bar, level_map, expectations_bar,
+                observables)                                       gradient of a cost written in those three outputs
 
 Julia's trailing ``!`` is spelled as a trailing underscore.  Arrays use the
 reference's column-major layouts (numpy ``order="F"``).
@@ -350,6 +352,24 @@ class DeviceProblem:
                                                           None if im is None else _vp(im), re.shape[2], _vp(out), _vp(out3)))
         self.last_scalars = out3
         return out
+
+    def eval_pullback(self, pcof=None, states_bar=None, populations_bar=None, level_map=None, expectations_bar=None,
+                      observables=None, history_precomputed=False):
+        """Pullback of the trajectory outputs to pcof: ``grad[n_pcof]``, the sum over the parts given of
+        ``<bar, d output / d pcof>`` with the cotangents ``states_bar`` (the shape of eval_states' result, or complex
+        ``[N, n_slots, n_cols]``, split as complex_to_real does), ``populations_bar`` (eval_populations', with the same
+        ``level_map``) and ``expectations_bar`` (eval_expectations', with the same ``observables``).  With ``bar = dJ/d output``
+        this is the gradient of any cost J written in those outputs.  Honours set_save_every; slot 0 is ignored.
+        ``history_precomputed``: reuse the stored forward sweep when it belongs to this pcof.  No target is needed."""
+        sb, pb, lm, eb, re, im = pullback_cotangents(self.N, self._slots(), self.c, states_bar, populations_bar, level_map,
+                                                     expectations_bar, observables)
+        pc, ptr, n = self._pcof_arg(pcof)
+        grad = np.zeros(self.n_pcof)
+        opt = lambda a: None if a is None else _vp(a)
+        _lib.check(self.h, self.lib.qgd_eval_pullback(self.h, ptr, n, 1 if history_precomputed else 0, opt(sb), opt(pb), opt(lm),
+                                                      0 if lm is None else lm.shape[0], opt(eb), opt(re), opt(im),
+                                                      0 if re is None else re.shape[2], _vp(grad)))
+        return grad
 
     def discrete_adjoint(self, pcof, history_precomputed=False, uv_history=None, lambda_history=None,
                          adjoint_forcing=None):
@@ -747,6 +767,75 @@ def eval_expectations(prob, controls, pcof, observables, order=2, saveEveryNstep
     dp.set_save_every(save)
     try:
         return dp.eval_expectations(observables, pcof)
+    finally:
+        dp.set_save_every(1)
+
+
+def pullback_cotangents(N, n_slots, n_cols, states_bar=None, populations_bar=None, level_map=None, expectations_bar=None,
+                        observables=None):
+    """The arguments of eval_pullback as the arrays the library takes, ``(states_bar, populations_bar, level_map,
+    expectations_bar, obs_re, obs_im)``: Fortran-ordered float64, None for what was not given.  ``states_bar``: real
+    ``[2N, n_slots, n_cols]`` or complex ``[N, n_slots, n_cols]`` (split as complex_to_real does: real parts on top);
+    ``populations_bar``: real ``[N, ..]``, or ``[n_groups, ..]`` with ``level_map`` ``[n_groups, N]``; ``expectations_bar``: real
+    ``[n_obs, ..]`` with ``observables`` as for observable_planes.  ValueError for a wrong shape or dtype, a cotangent that is
+    complex where its output is real, a level map or observables without their cotangent (or the reverse), an observable that
+    is not Hermitian, or no cotangent at all."""
+    tail = (int(n_slots), int(n_cols))
+
+    def real(a, rows, name):
+        a = np.asarray(a)
+        if a.dtype == bool or not np.issubdtype(a.dtype, np.number) or np.iscomplexobj(a):
+            raise ValueError(f"{name} must be a real numeric array; got dtype {a.dtype}")
+        if a.shape != (rows,) + tail:
+            raise ValueError(f"{name} must have shape {(rows,) + tail}; got {a.shape}")
+        return np.asfortranarray(a, dtype=np.float64)
+
+    if states_bar is None and populations_bar is None and expectations_bar is None:
+        raise ValueError("eval_pullback needs at least one of states_bar, populations_bar, expectations_bar")
+    sb = pb = lm = eb = re = im = None
+    if states_bar is not None:
+        sb = np.asarray(states_bar)
+        if sb.dtype == bool or not np.issubdtype(sb.dtype, np.number):
+            raise ValueError(f"states_bar must be numeric; got dtype {sb.dtype}")
+        rows = N if np.iscomplexobj(sb) else 2 * N
+        if sb.shape != (rows,) + tail:
+            raise ValueError(f"states_bar must be real {(2 * N,) + tail} or complex {(N,) + tail}; got {sb.dtype} {sb.shape}")
+        sb = complex_to_real(sb) if np.iscomplexobj(sb) else np.asfortranarray(sb, dtype=np.float64)
+    if level_map is not None:
+        if populations_bar is None:
+            raise ValueError("level_map given without populations_bar")
+        lm = np.asarray(level_map)
+        if lm.ndim != 2 or lm.shape[1] != N or lm.shape[0] < 1 or lm.dtype == bool or not np.issubdtype(lm.dtype, np.number) \
+                or np.iscomplexobj(lm):
+            raise ValueError(f"level_map must be a real [n_groups >= 1, {N}] array; got {lm.dtype} {lm.shape}")
+        lm = np.asfortranarray(lm, dtype=np.float64)
+    if populations_bar is not None:
+        pb = real(populations_bar, N if lm is None else lm.shape[0], "populations_bar")
+    if (expectations_bar is None) != (observables is None):
+        raise ValueError("expectations_bar and observables go together")
+    if expectations_bar is not None:
+        re, im = observable_planes(observables, N)
+        eb = real(expectations_bar, re.shape[2], "expectations_bar")
+    return sb, pb, lm, eb, re, im
+
+
+def eval_pullback(prob, controls, pcof, order=2, saveEveryNsteps=1, states_bar=None, populations_bar=None, level_map=None,
+                  expectations_bar=None, observables=None):
+    """Gradient with respect to pcof of a cost written in the outputs of eval_forward (its states as eval_states returns them),
+    eval_populations and eval_expectations: ``sum <bar, d output / d pcof>`` over the cotangents given, ``bar = d cost / d output``
+    in the shape of that output for the same ``saveEveryNsteps``, ``level_map`` and ``observables`` (DeviceProblem.eval_pullback,
+    DESIGN.md section 4g).  One forward and one adjoint sweep on the device, whatever the number of parameters.  Not in the
+    reference."""
+    save = int(saveEveryNsteps)
+    if save < 1:
+        raise ValueError("saveEveryNsteps must be a positive integer")
+    pullback_cotangents(prob.N_tot_levels, 1 + prob.nsteps // save, prob.N_initial_conditions, states_bar, populations_bar,
+                        level_map, expectations_bar, observables)      # (refusals before a handle is made or anything is uploaded)
+    dp = device_problem(prob, order)
+    dp.set_controls(controls)
+    dp.set_save_every(save)
+    try:
+        return dp.eval_pullback(pcof, states_bar, populations_bar, level_map, expectations_bar, observables)
     finally:
         dp.set_save_every(1)
 
