@@ -195,6 +195,41 @@ int qgd_eval_populations(qgd_handle h, const double *pcof, int32_t n_pcof, int32
 int qgd_eval_expectations(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
                           const double *obs_re, const double *obs_im, int32_t n_obs, double *expect, double *out3);
 
+/* Hermite dense output: the same three outputs BETWEEN the grid points, at `refine` points per step, from what the sweep already
+ * holds.  At every time point the device forms the m = order/2 scaled Taylor coefficients w_j = w^(j)/j! (Taylor indices 1..m of
+ * uv_history); the two-point Hermite interpolant of degree 2m+1 through the m+1 coefficients at both ends of step n,
+ *   w(t_n + theta dt) = sum_{j=0..m} dt^j [ A_j(theta) w_j(t_n) + (-1)^j A_j(1-theta) w_j(t_{n+1}) ],
+ *   A_j(theta) = theta^j (1-theta)^(m+1) sum_{k=0..m-j} C(m+k, k) theta^k,      theta = s / refine, s = 1 .. refine-1,
+ * has a local error O(dt^(2m+2)): the order of the method itself, for one memory-bound kernel (qgd_k_interp.hip) instead of a
+ * sweep on a `refine` times finer grid.  n_slots = 1 + nsteps * refine, slot k is time k dt / refine.  Slots k = n refine are the
+ * grid points, copied, not evaluated: refine = 1 returns what the corresponding call above returns, bit for bit.  The sums run
+ * in one fixed order: the same bits on every run.
+ *   The call runs the forward sweep exactly as qgd_eval_populations does (history_precomputed, pcof == NULL, out3, registered
+ * and unregistered out, resident and windowed grids -- every window interpolates its own steps), forms the stage derivatives
+ * if the stored sweep has none and hands the interpolated panels to the output kernels of the three calls above.  level_map /
+ * n_groups are read for QGD_DENSE_POPULATIONS only, obs_re / obs_im / n_obs for QGD_DENSE_EXPECTATIONS only, with the meaning
+ * they have above.  The result does NOT depend on qgd_set_save_every: every sub-point is returned.
+ *   Populations and expectation values are those OF THE INTERPOLATED STATE.  |psi(t)|^2 of the interpolant is not exactly
+ * norm-preserving between the grid points: it deviates from 1 at the size of the interpolation error.
+ *   The stored sweep is left as qgd_eval_forward without an output array leaves it, with the stage derivatives marked formed
+ * (refine > 1): a history_precomputed gradient, populations, expectations or pullback call that follows returns the bits it
+ * returned before, and the kept setup of qgd_eval_hessian_vec is voided only when the sweep is redone.  The interpolated panels
+ * ((1 + (nt-1) refine) Np 2cp doubles, nt the time points of the grid or of its longest window; 8 KB per sub-point at N = 64,
+ * 8 columns) stay on the handle, in one buffer: QGD_ERR_MEMORY when they do not fit the memory budget or the free device memory.
+ * No forcing argument: the forced sweep has no dense output.
+ * Refusals, before anything is launched.  QGD_ERR_ARGUMENT: NULL out, refine < 1 or 1 + nsteps * refine beyond int32, unknown
+ * kind, populations with level_map and n_groups < 1, expectations without obs_re or with n_obs < 1, a pcof of another length.
+ * QGD_ERR_STATE: history_precomputed without a previous forward evaluation, pcof without a control basis, no tables and no pcof.
+ * QGD_ERR_UNSUPPORTED: a handle with a communicator or a partition.  DESIGN.md section 4h. */
+#define QGD_DENSE_STATES       0   /* out [2N,       1 + nsteps*refine, n_cols] */
+#define QGD_DENSE_POPULATIONS  1   /* out [N or n_groups, ..]  (level_map as qgd_eval_populations) */
+#define QGD_DENSE_EXPECTATIONS 2   /* out [n_obs, ..]          (planes as qgd_eval_expectations)  */
+int qgd_eval_dense(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
+                   int32_t refine, int32_t kind,
+                   const double *level_map, int32_t n_groups,
+                   const double *obs_re, const double *obs_im, int32_t n_obs,
+                   double *out, double *out3);
+
 /* discrete_adjoint! (eval_grad_discrete_adjoint.jl:107-160): gradient of
  * infidelity + guard penalty (no ridge term, as the reference).  With
  * history_precomputed != 0 the forward sweep of the last evaluation is reused

@@ -275,6 +275,51 @@ function hip_eval_expectations(prob::SchrodingerProb, controls, pcof::Vector{Flo
     return expect
 end
 
+"Hermite dense output (qgd_eval_dense): the trajectory BETWEEN the grid points at `refine` points per step, slot k (1-based
+k+1) at time k*dt/refine, from the two-point Hermite interpolant of the stage derivatives the sweep forms anyway -- as accurate
+as the grid values themselves.  output = :states [2N, 1+nsteps*refine, N_initial_conditions], :populations ([N, ..], or
+[n_groups, ..] with level_map) or :expectations ([n_obs, ..] of `observables`, as hip_eval_expectations).  Slots 1:refine:end
+are the grid points, the bits of the grid-point calls.  Independent of saveEveryNsteps."
+function hip_eval_dense(prob::SchrodingerProb, controls, pcof::Vector{Float64}; order::Int=2, refine::Int=2,
+                        output::Symbol=:states, level_map::Union{Nothing,Matrix{Float64}}=nothing, observables=nothing,
+                        history_precomputed::Bool=false)
+    refine >= 1 || throw(ArgumentError("refine must be an integer >= 1"))
+    output in (:states, :populations, :expectations) || throw(ArgumentError("output must be :states, :populations or :expectations"))
+    (output == :expectations) == (observables !== nothing) || throw(ArgumentError("observables go with output = :expectations"))
+    level_map === nothing || output == :populations || throw(ArgumentError("level_map goes with output = :populations"))
+    N = prob.N_tot_levels
+    level_map === nothing || size(level_map, 2) == N || throw(DimensionMismatch("level_map must be [n_groups, $N]"))
+    n_obs, has_im = 0, false
+    obs_re, obs_im = zeros(0, 0, 0), zeros(0, 0, 0)
+    if observables !== nothing
+        obs = observables isa AbstractMatrix ? [observables] : collect(observables)
+        n_obs = length(obs)
+        n_obs >= 1 || throw(ArgumentError("no observable"))
+        obs_re, obs_im = zeros(N, N, n_obs), zeros(N, N, n_obs)
+        for (j, o) in enumerate(obs)
+            size(o) == (N, N) || throw(DimensionMismatch("observable $j must be [$N, $N]"))
+            O = Matrix{ComplexF64}(o)
+            maximum(abs, O - O') <= 1e-12 * max(1.0, maximum(abs, O)) || throw(ArgumentError("observable $j is not Hermitian"))
+            obs_re[:, :, j] = real(O); obs_im[:, :, j] = imag(O)
+        end
+        has_im = any(!iszero, obs_im)
+    end
+    rows = output == :states ? 2N : output == :expectations ? n_obs : (level_map === nothing ? N : size(level_map, 1))
+    kind = output == :states ? 0 : output == :populations ? 1 : 2
+    dp = device_problem(prob, order)
+    set_cost_type!(dp, :Infidelity)
+    pc_ptr, pc_len = set_controls!(dp, prob, controls, pcof)
+    out = zeros(rows, 1 + prob.nsteps * refine, prob.N_initial_conditions)
+    GC.@preserve pcof level_map obs_re obs_im check(dp.handle, ccall((:qgd_eval_dense, libqgd), Cint,
+          (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32,
+           Ptr{Float64}, Ptr{Float64}),
+          dp.handle, pc_ptr, pc_len, history_precomputed ? 1 : 0, refine, kind,
+          level_map === nothing ? Ptr{Float64}(C_NULL) : pointer(level_map), level_map === nothing ? 0 : size(level_map, 1),
+          n_obs > 0 ? pointer(obs_re) : Ptr{Float64}(C_NULL), has_im ? pointer(obs_im) : Ptr{Float64}(C_NULL), n_obs,
+          out, dp.last_out3))
+    return out
+end
+
 "Gradient with respect to pcof of a cost written in the outputs of hip_eval_states, hip_get_populations and
 hip_eval_expectations (qgd_eval_pullback): sum of <bar, d output / d pcof> over the cotangents given, each in the shape of its
 output for the same saveEveryNsteps, level_map and observables.  states_bar [2N, slots, c]; populations_bar [N or n_groups,

@@ -252,6 +252,11 @@ int qgdk_populations(const qgdk_ctx *c, const double *panels, long long src_n, d
    ([N x N x n_obs] column-major on the device; obs_im null: real symmetric observables), summed in a fixed order */
 int qgdk_expectations(const qgdk_ctx *c, const double *panels, long long src_n, double *out, long long dst_col,
                       long long dst_n, int n_cnt, const double *obs_re, const double *obs_im, int n_obs, hipStream_t stream);
+/* qgd_k_interp.hip: Hermite dense output.  State panels hist [nt][Np][2cp] and stage derivatives dpsi [nt][m][Np][2cp] of c's nt
+   time points -> out [1 + (nt-1) refine][Np][2cp], slot n refine + s at time (n + s / refine) dt; grid slots are copies, padding
+   rows and columns zeros.  w_dev [refine-1][m+1][2]: the weights of the left and right end with dt^j folded in */
+int qgdk_interp(const qgdk_ctx *c, const double *hist, const double *dpsi, double *out, int refine, const double *w_dev,
+                hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,12 @@ struct qgd_handle_s {
     } pb;
     std::vector<void *> pullback_bufs;
     std::vector<size_t> pullback_key;  // (nt, n_pcof, and the lengths of the five uploads) they were sized for; empty: none
+    // qgd_eval_dense: the interpolated panels [1 + (points-1) refine][Np][2cp] of a resident grid or of the
+    // longest window, and the weight table of qgd_k_interp.hip with its host copy (the upload reads it)
+    double *dense_panels = nullptr, *dense_w = nullptr;
+    std::vector<double> dense_w_host;
+    std::vector<void *> dense_bufs;
+    std::vector<size_t> dense_key;     // (time points, refine, panel size, m, bits of dt) they were made for; empty: none
     std::vector<void *> forcing_bufs;  // eval_forward with a user forcing
     double *fsc_forcing = nullptr;     // (in forcing_bufs) the same slab for k_forcing_terms
     size_t forcing_key = 0;
@@ -370,8 +376,10 @@ RcclApi &rccl();
 // themselves [2N, slots, c], the level populations [N, slots, c] (n_groups = 0) or their contraction with the level map on the
 // device [n_groups, slots, c], or the expectation values [n_obs, slots, c] of the observables whose planes lie in obs_planes
 // (obs_im: imaginary planes behind the real ones)
+// refine = 0: of the grid points, every qgd_set_save_every-th (the three calls above).  refine = r >= 1 (qgd_eval_dense): of the
+// Hermite dense output, slot k at time k dt / r, every slot whatever qgd_set_save_every says; r = 1 is the grid points themselves
 enum ObserveKind { OBS_STATES, OBS_POPULATIONS, OBS_EXPECTATIONS };
-struct Observe { ObserveKind kind; int n_groups; double *out; int n_obs; bool obs_im; };
+struct Observe { ObserveKind kind; int n_groups; double *out; int n_obs; bool obs_im; int refine = 0; };
 
 // A buffer plan: the device buffers of a keyed pool, each listed once -- where its pointer goes, its length in doubles, whether
 // this problem has it (else the pointer is set to NULL).  plan_bytes: what the plan asks for (without dev_alloc's pad);
@@ -395,6 +403,7 @@ int history_out(qgd_handle h, double *uv_history, int save = 1);
 int panels_out(qgd_handle h, const double *panels, double **stage, double *out, size_t J, int n_first);
 int lambda_history_out(qgd_handle h, double *out);
 int observe_out(qgd_handle h, const Observe &obs, int save);
+int dense_buffers(qgd_handle h, int refine);
 
 // qgd_host_eval.cpp
 int upload_pcof(qgd_handle h, const double *pcof, int n_pcof);

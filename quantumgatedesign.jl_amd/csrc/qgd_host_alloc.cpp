@@ -37,8 +37,8 @@ int plan_alloc(qgd_handle h, std::vector<void *> &pool, const std::vector<Buf> &
 // the buffers of the forced gradient, the Hessian and the Hessian-vector product follow the grid and the control basis
 void free_sensitivity_buffers(qgd_handle h)
 {
-    for (auto *pool : {&h->forced_bufs, &h->hess_bufs, &h->hvp_bufs, &h->pullback_bufs}) free_pool(*pool);
-    h->forced_key = h->hess_key = h->hvp_key = 0; h->pullback_key.clear(); hvp_void(h);
+    for (auto *pool : {&h->forced_bufs, &h->hess_bufs, &h->hvp_bufs, &h->pullback_bufs, &h->dense_bufs}) free_pool(*pool);
+    h->forced_key = h->hess_key = h->hvp_key = 0; h->pullback_key.clear(); h->dense_key.clear(); hvp_void(h);
 }
 
 
@@ -543,7 +543,7 @@ void qgd_destroy(qgd_handle h)
     if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
     for (auto &r : h->regs) (void)hipHostUnregister(r.host);
     free_pool(h->stage_bufs);
-    free_pool(h->static_bufs); free_pool(h->grid_bufs); free_pool(h->basis_bufs); free_pool(h->forced_bufs); free_pool(h->hess_bufs); free_pool(h->hvp_bufs); free_pool(h->pullback_bufs); free_pool(h->forcing_bufs);
+    free_pool(h->static_bufs); free_pool(h->grid_bufs); free_pool(h->basis_bufs); free_pool(h->forced_bufs); free_pool(h->hess_bufs); free_pool(h->hvp_bufs); free_pool(h->pullback_bufs); free_pool(h->dense_bufs); free_pool(h->forcing_bufs);
     for (auto &p : h->phases) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     if (h->host_out) (void)hipHostFree(h->host_out);
     if (h->host_in) (void)hipHostFree(h->host_in);

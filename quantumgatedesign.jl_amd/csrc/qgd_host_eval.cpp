@@ -459,10 +459,11 @@ static int observe_eval(qgd_handle h, const double *pcof, int n_pcof, int histor
 {
     qgdk_ctx &k = h->k;
     int rc;
+    const int save = obs.refine ? 1 : h->save_every;      // (the dense output returns every sub-point)
     if (history_precomputed && h->sweep.kind == SWEEP_NONE)
         return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
     if (h->chunks_eff > 1) {      // one window is resident at a time: the pass over the windows is redone, each hands out its share
-        if ((rc = chunked_forward(h, pcof, n_pcof, nullptr, h->save_every, &obs))) return rc;
+        if ((rc = chunked_forward(h, pcof, n_pcof, nullptr, save, &obs))) return rc;
         return fetch_results(h, nullptr, out3);
     }
     struct CopyGuard { qgd_handle h; ~CopyGuard() { (void)finish_copies(h); } } guard{h};      // no copy outlives the call
@@ -470,7 +471,7 @@ static int observe_eval(qgd_handle h, const double *pcof, int n_pcof, int histor
         // (the overlaps in out3 belong to the present target, which may have been set after the sweep)
         PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target));
     } else if ((rc = run_forward(h, pcof, n_pcof, true))) return rc;
-    if ((rc = observe_out(h, obs, h->save_every))) return rc;
+    if ((rc = observe_out(h, obs, save))) return rc;
     if ((rc = fetch_results(h, nullptr, out3))) return rc;
     return finish_copies(h);
 }
@@ -526,6 +527,52 @@ int qgd_eval_expectations(qgd_handle h, const double *pcof, int32_t n_pcof, int3
     HIP_TRY(h, hipMemcpyAsync(h->obs_planes, obs_re, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
     if (obs_im) HIP_TRY(h, hipMemcpyAsync(h->obs_planes + len, obs_im, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
     return observe_eval(h, pcof, n_pcof, history_precomputed, Observe{OBS_EXPECTATIONS, 0, expect, n_obs, obs_im != nullptr}, out3);
+}
+
+
+// Hermite dense output: the sweep of the three calls above, then the states, populations or expectation
+// values of the interpolant at refine points per step (observe_out: stage derivatives, qgd_k_interp.hip, the same output kernels
+// and transport).  Everything that can refuse the call does so here, before the first launch or upload.
+int qgd_eval_dense(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed, int32_t refine, int32_t kind,
+                   const double *level_map, int32_t n_groups, const double *obs_re, const double *obs_im, int32_t n_obs,
+                   double *out, double *out3)
+{
+    if (!h) return QGD_ERR_ARGUMENT;
+    if (!out) return fail(h, QGD_ERR_ARGUMENT, "null output array");
+    if (refine < 1 || (long long)h->nsteps * refine + 1 > 0x7fffffffLL)
+        return fail(h, QGD_ERR_ARGUMENT, "refine must be >= 1 and 1 + nsteps * refine fit a 32-bit integer");
+    if (kind != QGD_DENSE_STATES && kind != QGD_DENSE_POPULATIONS && kind != QGD_DENSE_EXPECTATIONS)
+        return fail(h, QGD_ERR_ARGUMENT, "unknown kind of dense output");
+    if (kind == QGD_DENSE_POPULATIONS && level_map && n_groups < 1) return fail(h, QGD_ERR_ARGUMENT, "a level map needs n_groups >= 1");
+    if (kind == QGD_DENSE_EXPECTATIONS && (!obs_re || n_obs < 1)) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_dense needs obs_re and n_obs >= 1 for expectation values");
+    HIP_TRY(h, hipSetDevice(h->device));
+    NEED_GRID(h);
+    const qgdk_ctx &k = h->k;
+    if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_dense is single-GPU: this handle has a communicator or a partition");
+    if (pcof && !h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before passing pcof");
+    if (pcof && n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
+    if (!pcof && !h->have_tables && k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
+    if (history_precomputed && h->sweep.kind == SWEEP_NONE)
+        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+    int rc;
+    if (refine > 1 && (rc = dense_buffers(h, refine))) return rc;      // (QGD_ERR_MEMORY before the sweep is touched)
+    Observe obs{OBS_STATES, 0, out, 0, false, refine};
+    if (kind == QGD_DENSE_POPULATIONS) {
+        obs.kind = OBS_POPULATIONS;
+        if (level_map) {
+            const size_t len = (size_t)n_groups * k.N;
+            if ((rc = grow_stage(h, &h->obs_map, &h->obs_map_len, len))) return rc;
+            HIP_TRY(h, hipMemcpyAsync(h->obs_map, level_map, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
+            obs.n_groups = n_groups;
+        }
+    } else if (kind == QGD_DENSE_EXPECTATIONS) {
+        obs.kind = OBS_EXPECTATIONS; obs.n_obs = n_obs; obs.obs_im = obs_im != nullptr;
+        const size_t len = (size_t)n_obs * k.N * k.N;
+        if ((rc = grow_stage(h, &h->obs_planes, &h->obs_planes_len, (obs_im ? 2 : 1) * len))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->obs_planes, obs_re, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
+        if (obs_im) HIP_TRY(h, hipMemcpyAsync(h->obs_planes + len, obs_im, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
+    }
+    return observe_eval(h, pcof, n_pcof, history_precomputed, obs, out3);
 }
 
 

@@ -79,12 +79,15 @@ struct Span {
     size_t slots;                     // slots of the caller's array along time
 };
 
-static Span span_of(qgd_handle h, int save, int n_first)
+// (refine = r > 1: the points are those of the Hermite dense output, r per step -- the buffers' nt points stand for the
+//  1 + (nt-1) r of qgd_k_interp.hip's panels, a window's first one at n_off r)
+static Span span_of(qgd_handle h, int save, int n_first, int refine = 1)
 {
     const qgdk_ctx &k = h->k;
     const bool windowed = h->chunks_eff > 1;
-    const size_t sv = (size_t)save, base = windowed ? (size_t)k.n_off : 0, total = windowed ? (size_t)k.nt_glob : (size_t)k.nt;
-    const size_t g_lo = base + (size_t)n_first, g_hi = base + (size_t)k.nt - 1;      // global points on offer
+    const size_t sv = (size_t)save, rf = (size_t)refine, base = windowed ? (size_t)k.n_off * rf : 0;
+    const size_t total = ((windowed ? (size_t)k.nt_glob : (size_t)k.nt) - 1) * rf + 1, held = ((size_t)k.nt - 1) * rf + 1;
+    const size_t g_lo = base + (size_t)n_first, g_hi = base + held - 1;      // global points on offer
     const size_t s_lo = (g_lo + sv - 1) / sv, s_hi = g_hi / sv;                      // the slots they fill
     const size_t slots = 1 + (total - 1) / sv;
     if (s_hi < s_lo) return Span{0, 0, sv, s_lo, slots};
@@ -228,21 +231,82 @@ int lambda_history_out(qgd_handle h, double *out)
 }
 
 
+// Weights of the two-point Hermite interpolant of degree 2m+1 (qgd_k_interp.hip) at theta = s / r, s = 1 .. r-1, as the kernel
+// reads them: w[s-1][j][0] = dt^j A_j(theta), w[s-1][j][1] = (-dt)^j A_j(1 - theta),
+// A_j(x) = x^j (1-x)^(m+1) sum_{k=0..m-j} C(m+k, k) x^k.  Every term is non-negative on [0, 1]: no cancellation.
+static void dense_weights(std::vector<double> &w, int m, int r, double dt)
+{
+    w.assign((size_t)2 * (m + 1) * (r - 1), 0.0);
+    auto A = [m](int j, double x, double y) {      // y = 1 - x, formed without rounding the difference
+        double sum = 0.0, binom = 1.0, xk = 1.0;
+        for (int k = 0; k <= m - j; k++) { sum += binom * xk; binom = binom * (m + k + 1) / (k + 1); xk *= x; }
+        return std::pow(x, j) * std::pow(y, m + 1) * sum;
+    };
+    for (int s = 1; s < r; s++) {
+        const double x = (double)s / r, y = (double)(r - s) / r;
+        for (int j = 0; j <= m; j++) {
+            w[((size_t)(s - 1) * (m + 1) + j) * 2] = std::pow(dt, j) * A(j, x, y);
+            w[((size_t)(s - 1) * (m + 1) + j) * 2 + 1] = std::pow(-dt, j) * A(j, y, x);
+        }
+    }
+}
+
+
+// buffers of qgd_eval_dense (refine > 1): the interpolated panels of a resident grid, or of the longest window of a windowed
+// one, and the weight table.  Kept on the handle under a key, freed with the sensitivity buffers; QGD_ERR_MEMORY when they do
+// not fit the memory budget or the free device memory.  (One buffer, no slabs: 8 KB per sub-point at cnot3.)  The key holds all
+// that sizes or fills them: the points, refine, the panel size, m and dt.
+int dense_buffers(qgd_handle h, int refine)
+{
+    const qgdk_ctx &k = h->k;
+    const size_t hstep = (size_t)k.Np * 2 * k.cp, P = stage_points(h), pts = 1 + (P - 1) * (size_t)refine;
+    size_t dt_bits = 0;
+    memcpy(&dt_bits, &k.dt, sizeof(double) < sizeof(size_t) ? sizeof(double) : sizeof(size_t));
+    const std::vector<size_t> key = {P, (size_t)refine, hstep, (size_t)k.m, dt_bits};
+    if (h->dense_key == key) return QGD_OK;
+    h->dense_key.clear();
+    free_pool(h->dense_bufs);
+    const std::vector<Buf> plan = {{&h->dense_panels, pts * hstep}, {&h->dense_w, (size_t)2 * (k.m + 1) * (refine - 1)}};
+    size_t bytes = plan_bytes(plan), fr = 0, tot = 0;
+    if ((h->mem_budget && bytes > h->mem_budget) || (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr))
+        return fail(h, QGD_ERR_MEMORY, "the interpolated panels of qgd_eval_dense do not fit (" + std::to_string(bytes) + " bytes needed)");
+    int rc = plan_alloc(h, h->dense_bufs, plan);
+    if (rc) return rc;
+    dense_weights(h->dense_w_host, k.m, refine, k.dt);
+    HIP_TRY(h, hipMemcpyAsync(h->dense_w, h->dense_w_host.data(), h->dense_w_host.size() * sizeof(double), hipMemcpyHostToDevice, k.stream));
+    h->dense_key = key;
+    return QGD_OK;
+}
+
+
 // qgd_eval_states / qgd_eval_populations / qgd_eval_expectations: the state panels hist [nt][Np][2cp] in the buffers -> the
 // caller's [rows, slots, c], rows = 2N (the states: Taylor index 0 of uv_history, through the same re-layout kernel), N (level
 // populations), n_groups (populations contracted with the level map in obs_map) or n_obs (expectation values of the observables
 // in obs_planes).  No stage derivatives, a staging buffer of exactly the bytes that leave.
+// qgd_eval_dense with refine > 1: the stage derivatives are formed where the sweep has none, qgd_k_interp.hip turns the buffers'
+// nt points into 1 + (nt-1) refine panels of the same layout, and those take the place of hist (save = 1).
 int observe_out(qgd_handle h, const Observe &obs, int save)
 {
     qgdk_ctx &k = h->k;
     const size_t hstep = (size_t)k.Np * 2 * k.cp;
     const size_t rows = obs.kind == OBS_STATES ? 2 * (size_t)k.N : obs.kind == OBS_EXPECTATIONS ? (size_t)obs.n_obs
                       : (obs.n_groups > 0 ? (size_t)obs.n_groups : (size_t)k.N);
-    const Span sp = span_of(h, save, 0);
+    const bool dense = obs.refine > 1;
+    const Span sp = span_of(h, save, 0, dense ? obs.refine : 1);
     if (!sp.count) return QGD_OK;
-    int rc = grow_stage(h, &h->stage_obs, &h->stage_obs_len, rows * sp.count * k.c);
-    if (rc) return rc;
-    const double *src = k.hist + sp.first * hstep;
+    int rc;
+    const double *panels = k.hist;
+    if (dense) {
+        // (qgd_eval_dense made the buffers for the longest window before the sweep: this finds them under their key and
+        //  allocates nothing, so QGD_ERR_MEMORY is decided there, before anything ran)
+        if ((rc = dense_buffers(h, obs.refine))) return rc;
+        if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
+        PhaseTimer t(h, "dense_output");
+        K_TRY(h, qgdk_interp(&k, k.hist, k.dpsi, h->dense_panels, obs.refine, h->dense_w, k.stream));
+        panels = h->dense_panels;
+    }
+    if ((rc = grow_stage(h, &h->stage_obs, &h->stage_obs_len, rows * sp.count * k.c))) return rc;
+    const double *src = panels + sp.first * hstep;
     if (obs.kind == OBS_STATES) {
         K_TRY(h, qgdk_layout(&k, src, (long long)(hstep * sp.stride), 0, h->stage_obs, (long long)(sp.count * rows), (long long)rows, 0, 0, (int)sp.count, 1, 0, k.stream, 0));
     } else if (obs.kind == OBS_EXPECTATIONS) {

@@ -13,6 +13,8 @@ behaviour as the reference:
   eval_expectations(prob, controls, pcof, observables; order, saveEveryNsteps)   Re(psi^H O psi) along the sweep, on the device
   eval_pullback(prob, controls, pcof; order, saveEveryNsteps, states_bar, populations_bar, level_map, expectations_bar,
                 observables)                                       gradient of a cost written in those three outputs
+  eval_dense(prob, controls, pcof; order, refine, output, level_map, observables)   the same outputs between the grid points
+                                                                   (Hermite dense output; hermite_interpolate is its statement)
 
 Julia's trailing ``!`` is spelled as a trailing underscore.  Arrays use the
 reference's column-major layouts (numpy ``order="F"``).
@@ -352,6 +354,50 @@ class DeviceProblem:
                                                           None if im is None else _vp(im), re.shape[2], _vp(out), _vp(out3)))
         self.last_scalars = out3
         return out
+
+    # -- Hermite dense output (qgd_eval_dense) ----------------------------------------------------------
+    def _eval_dense(self, kind, rows, refine, pcof, history_precomputed, out, lm=None, re=None, im=None):
+        shape = (rows, 1 + self.nsteps * refine, self.c)
+        out = np.zeros(shape, order="F") if out is None else _check_out(out, shape, "out")
+        out3 = np.zeros(3)
+        pc, ptr, n = self._pcof_arg(pcof)
+        opt = lambda a: None if a is None else _vp(a)
+        _lib.check(self.h, self.lib.qgd_eval_dense(self.h, ptr, n, 1 if history_precomputed else 0, refine, kind, opt(lm),
+                                                   0 if lm is None else lm.shape[0], opt(re), opt(im),
+                                                   0 if re is None else re.shape[2], _vp(out), _vp(out3)))
+        self.last_scalars = out3
+        return out
+
+    def eval_dense_states(self, refine, pcof=None, history_precomputed=False, out=None):
+        """The state trajectory at ``refine`` points per step, ``[2N, 1 + nsteps * refine, n_cols]`` (Fortran order), slot k at
+        time ``k * dt / refine``: the two-point Hermite interpolant of the stage derivatives the sweep forms anyway
+        (hermite_interpolate is the statement of what the device computes), as accurate as the run itself.  Slots ``::refine``
+        are the grid points, the bits eval_states returns.  Independent of set_save_every.  ``history_precomputed``: reuse the
+        stored forward sweep when it belongs to this pcof.  The scalars of the call are left in ``self.last_scalars``."""
+        refine = check_refine(refine)
+        return self._eval_dense(0, 2 * self.N, refine, pcof, history_precomputed, out)
+
+    def eval_dense_populations(self, refine, pcof=None, level_map=None, history_precomputed=False, out=None):
+        """Level populations of the interpolated state (eval_dense_states), ``[N, 1 + nsteps * refine, n_cols]``, or with
+        ``level_map`` ``[n_groups, N]`` their contraction ``[n_groups, ..]``, as eval_populations.  Between the grid points they
+        sum to 1 only to the accuracy of the interpolant."""
+        refine = check_refine(refine)
+        rows, lm = self.N, None
+        if level_map is not None:
+            lm = np.asarray(level_map)
+            if lm.ndim != 2 or lm.shape[1] != self.N or lm.shape[0] < 1 or not np.issubdtype(lm.dtype, np.number) \
+                    or np.iscomplexobj(lm):
+                raise ValueError(f"level_map must be a real [n_groups >= 1, {self.N}] array; got {lm.dtype} {lm.shape}")
+            lm = np.asfortranarray(lm, dtype=np.float64)
+            rows = lm.shape[0]
+        return self._eval_dense(1, rows, refine, pcof, history_precomputed, out, lm=lm)
+
+    def eval_dense_expectations(self, refine, observables, pcof=None, history_precomputed=False, out=None):
+        """Expectation values ``Re(psi^H O_j psi)`` of the interpolated state (eval_dense_states),
+        ``[n_obs, 1 + nsteps * refine, n_cols]``; ``observables`` as for eval_expectations."""
+        refine = check_refine(refine)
+        re, im = observable_planes(observables, self.N)
+        return self._eval_dense(2, re.shape[2], refine, pcof, history_precomputed, out, re=re, im=im)
 
     def eval_pullback(self, pcof=None, states_bar=None, populations_bar=None, level_map=None, expectations_bar=None,
                       observables=None, history_precomputed=False):
@@ -769,6 +815,98 @@ def eval_expectations(prob, controls, pcof, observables, order=2, saveEveryNstep
         return dp.eval_expectations(observables, pcof)
     finally:
         dp.set_save_every(1)
+
+
+def check_refine(refine):
+    """``refine`` of the dense output as an int; ValueError unless it is an integer >= 1 (a bool or a float with a fraction is not)."""
+    if isinstance(refine, (bool, np.bool_)) or not isinstance(refine, (int, np.integer)):
+        if not (isinstance(refine, (float, np.floating)) and float(refine).is_integer()):
+            raise ValueError(f"refine must be an integer >= 1; got {refine!r}")
+    if int(refine) < 1:
+        raise ValueError(f"refine must be an integer >= 1; got {refine!r}")
+    return int(refine)
+
+
+def hermite_dense_weights(m, refine, dt):
+    """Weights of the two-point Hermite interpolant of degree ``2m+1`` at ``theta = s / refine``, ``s = 1 .. refine-1``: the
+    tables ``(a, b)``, each ``[refine-1, m+1]``, with ``a[s-1, j] = dt^j A_j(theta)`` (left end of the step) and
+    ``b[s-1, j] = (-dt)^j A_j(1-theta)`` (right end), ``A_j(x) = x^j (1-x)^(m+1) sum_{k=0..m-j} C(m+k, k) x^k``.  Every term of
+    ``A_j`` is non-negative on [0, 1].  ``m = 1``: the cubic Hermite basis."""
+    from math import comb
+    m, refine = int(m), check_refine(refine)
+    if m < 1:
+        raise ValueError("m must be >= 1")
+    a, b = np.zeros((refine - 1, m + 1)), np.zeros((refine - 1, m + 1))
+
+    def A(j, x, y):                                       # y = 1 - x, formed without rounding the difference
+        return x ** j * y ** (m + 1) * sum(comb(m + k, k) * x ** k for k in range(m - j + 1))
+
+    for s in range(1, refine):
+        x, y = s / refine, (refine - s) / refine
+        for j in range(m + 1):
+            a[s - 1, j] = dt ** j * A(j, x, y)
+            b[s - 1, j] = (-dt) ** j * A(j, y, x)
+    return a, b
+
+
+def hermite_interpolate(uv_history, dt, refine):
+    """Hermite dense output of a history ``[2N, 1+m, nt, n_cols]`` of scaled Taylor coefficients ``w_j = w^(j)/j!`` (what
+    eval_forward_ fills, from the device or from any other Hermite integrator): ``[2N, 1 + (nt-1) * refine, n_cols]`` (Fortran order), slot ``n * refine + s`` at
+    time ``(n + s / refine) dt``,
+        ``w = sum_{j=0..m} a[s-1, j] w_j(t_n) + b[s-1, j] w_j(t_{n+1})``       (hermite_dense_weights),
+    summed over ascending j, left end before right end; slots ``n * refine`` are copies of ``uv_history[:, 0, n]``.  Local error
+    ``O(dt^(2m+2))``, the order of the method.  Host arithmetic: the written statement of what eval_dense computes on the device."""
+    h = np.asarray(uv_history)
+    if h.ndim != 4 or h.shape[1] < 2 or h.shape[2] < 1 or not np.issubdtype(h.dtype, np.floating):
+        raise ValueError("uv_history must be a real array [2N, 1+m, nt, n_cols] with m >= 1")
+    refine = check_refine(refine)
+    m, nt = h.shape[1] - 1, h.shape[2]
+    out = np.zeros((h.shape[0], 1 + (nt - 1) * refine, h.shape[3]), order="F")
+    out[:, ::refine] = h[:, 0]
+    a, b = hermite_dense_weights(m, refine, float(dt))
+    for s in range(1, refine):
+        acc = np.zeros((h.shape[0], nt - 1, h.shape[3]))
+        for j in range(m + 1):
+            acc = acc + a[s - 1, j] * h[:, j, :-1]
+            acc = acc + b[s - 1, j] * h[:, j, 1:]
+        out[:, s::refine] = acc
+    return out
+
+
+def dense_times(prob, refine):
+    """The ``1 + nsteps * refine`` time stamps of the dense output of ``prob``: slot k at ``k * tf / (nsteps * refine)``."""
+    refine = check_refine(refine)
+    n = prob.nsteps * refine
+    return np.arange(n + 1) * (prob.tf / n)
+
+
+def eval_dense(prob, controls, pcof, order=2, refine=2, output="states", level_map=None, observables=None):
+    """The trajectory between the grid points: ``output="states"`` ``[2N, 1 + nsteps * refine, N_initial_conditions]``,
+    ``"populations"`` (``[N, ..]``, or ``[n_groups, ..]`` with ``level_map``) or ``"expectations"`` (``[n_obs, ..]`` of
+    ``observables``, as eval_expectations) of the Hermite interpolant of the order-``order`` sweep at ``refine`` points per step
+    (DeviceProblem.eval_dense_states); dense_times gives the time stamps.  As accurate as the grid values
+    themselves, for one memory-bound kernel instead of a sweep on a ``refine`` times finer grid.  Not in the reference."""
+    refine = check_refine(refine)
+    if output not in ("states", "populations", "expectations"):
+        raise ValueError("output must be 'states', 'populations' or 'expectations'")
+    if (output == "expectations") != (observables is not None):
+        raise ValueError("observables go with output='expectations'")
+    if level_map is not None and output != "populations":
+        raise ValueError("level_map goes with output='populations'")
+    N = prob.N_tot_levels
+    if observables is not None:
+        observable_planes(observables, N)                 # (refusals before a handle is made or anything is uploaded)
+    if level_map is not None:
+        lm = np.asarray(level_map)
+        if lm.ndim != 2 or lm.shape[1] != N or lm.shape[0] < 1 or not np.issubdtype(lm.dtype, np.number) or np.iscomplexobj(lm):
+            raise ValueError(f"level_map must be a real [n_groups >= 1, {N}] array; got {lm.dtype} {lm.shape}")
+    dp = device_problem(prob, order)
+    dp.set_controls(controls)
+    if output == "states":
+        return dp.eval_dense_states(refine, pcof)
+    if output == "populations":
+        return dp.eval_dense_populations(refine, pcof, level_map=level_map)
+    return dp.eval_dense_expectations(refine, observables, pcof)
 
 
 def pullback_cotangents(N, n_slots, n_cols, states_bar=None, populations_bar=None, level_map=None, expectations_bar=None,
