@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <chrono>
 #include <string>
 #include <vector>
@@ -72,6 +73,24 @@ struct StoredSweep {
     bool front = false;
 };
 
+// A buffer plan: the device buffers of a keyed pool, each listed once -- where its pointer goes (its slot), its length in doubles,
+// whether this problem has it (else the slot is set to NULL).  plan_bytes: what the plan asks for (without dev_alloc's pad).
+// A pool of on-demand device buffers: the allocations, the slots their pointers were handed to (with the length that goes with
+// a grow-to-largest buffer's pointer, Grown) and the exact tuple they were made for (empty: nothing allocated under a key).
+// pool_release frees them, writes NULL (and length 0) into every slot and clears the key; pool_missing: the bytes pool_ensure
+// would allocate for a (key, plan) pair.  The other functions are in qgd_host_alloc.cpp.
+struct Buf { double **slot; size_t count; bool on = true; };
+inline size_t plan_bytes(const std::vector<Buf> &plan) { size_t n = 0; for (const Buf &b : plan) n += b.on ? b.count : 0; return n * sizeof(double); }
+struct Grown { double *p = nullptr; size_t len = 0; };
+struct Pool {
+    struct Held { void *mem; double **slot; size_t *len; };
+    std::vector<Held> held;
+    std::vector<size_t> key;
+};
+struct KeyedPlan { std::vector<size_t> key; std::vector<Buf> plan; };
+inline size_t pool_missing(const Pool &pool, const KeyedPlan &p) { return pool.key == p.key ? 0 : plan_bytes(p.plan); }
+enum { POOL_FORCED, POOL_HESS, POOL_HVP, POOL_PULLBACK, POOL_DENSE, N_SENS_POOLS, POOL_FORCING = N_SENS_POOLS, POOL_STAGE, N_POOLS };
+
 struct qgd_handle_s {
     qgdk_ctx k{};
     int order = 0, nsteps = 0, device = 0;      // nsteps: GLOBAL number of timesteps
@@ -80,24 +99,30 @@ struct qgd_handle_s {
     bool timing = false;                // per-phase HIP events are opt-in (qgd_set_timing): 26 event records cost ~0.17 ms
     std::string timing_only;            // when non-empty: only this phase is bracketed by events
     std::string err;
-    std::vector<void *> static_bufs, grid_bufs, basis_bufs, forced_bufs;
+    std::vector<void *> static_bufs, grid_bufs, basis_bufs;
+    // The device buffers that entry points make on demand, one pool per row.  An entry point ensures its pool under the exact
+    // tuple of what sizes or fills it; the pointers below are the pools' slots, NULL whenever their pool is released.  alloc_grid
+    // releases every pool, qgd_set_control_basis the sensitivity pools (free_sensitivity_buffers).
+    //   POOL_FORCED    forced gradient (k.fs_*, fsc_forced), also under the two second-order entry points; key (nt, n_pcof, scan blocks)
+    //   POOL_HESS      qgd_eval_hessian: sensitivity history, work buffers of qgd_k_hessian.hip (hs); key (nt, n_pcof, basis directions, general guard)
+    //   POOL_HVP       qgd_eval_hessian_vec (hv); that key and the scan blocks
+    //   POOL_PULLBACK  qgd_eval_pullback (pb); key (nt, n_pcof, the lengths of the five uploads)
+    //   POOL_DENSE     qgd_eval_dense (dense_panels, dense_w); key (time points, refine, panel size, m, bits of dt)
+    //   POOL_FORCING   qgd_eval_forward with a user forcing (k.ff_*, fsc_forcing); key (nt, scan blocks)
+    //   POOL_STAGE     the staging buffers of the reference-layout outputs: no key, each made or grown on first need
+    Pool pools[N_POOLS];
     std::vector<double> target_host;   // stacked real target [2N x c] (forced gradient: the overlaps are host arithmetic)
-    size_t forced_key = 0;             // (nt, n_pcof) the forced-gradient buffers were sized for
-    double *fsc_forced = nullptr;      // (in forced_bufs) HBM work-panel slab of k_forced_basis when its panels exceed the LDS (N > 64)
-    std::vector<void *> hess_bufs;     // qgd_eval_hessian: sensitivity history and the work buffers of qgd_k_hessian.hip
-    size_t hess_key = 0;               // (nt, n_pcof, basis directions, general guard) they were sized for
+    double *fsc_forced = nullptr, *fsc_forcing = nullptr;      // HBM work-panel slabs of k_forced_basis / k_forcing_terms when their panels exceed the LDS (N > 64)
     struct HessBufs { double *shist = nullptr, *ws = nullptr, *Z = nullptr, *half = nullptr, *slab = nullptr, *zt = nullptr, *Y = nullptr; } hs;
     // qgd_eval_hessian_vec: the direction-independent setup of a product -- forward sweep, lambda, stage
-    // derivatives, the forced basis responses (in forced_bufs), Z and the halves of e_n -- stays on the handle.  hvp_valid: it
+    // derivatives, the forced basis responses (in POOL_FORCED), Z and the halves of e_n -- stays on the handle.  hvp_valid: it
     // belongs to the stored sweep (StoredSweep::pcof) and the present target, cost type, basis and grid; every transition of
     // the sweep record clears it (hvp_void), as do the setters that free these buffers.
     struct HvpBufs {
         double *Z = nullptr, *half = nullptr, *slab = nullptr, *sv = nullptr, *ws = nullptr, *F = nullptr, *Y = nullptr, *mu = nullptr;
         double *phi = nullptr, *bnd = nullptr, *gvt = nullptr, *term = nullptr, *part = nullptr, *v = nullptr, *gB = nullptr, *out = nullptr, *scal = nullptr;
-        void *one3 = nullptr;
+        double *one3 = nullptr;        // (16 bytes: the one-operator, one-coefficient basis of the direction table)
     } hv;
-    std::vector<void *> hvp_bufs;
-    size_t hvp_key = 0;                // (nt, n_pcof, basis directions, general guard, scan blocks) they were sized for
     bool hvp_valid = false;
     std::vector<double> hvp_grad;      // the adjoint gradient of the setup
     // qgd_eval_pullback: the forcing, y and mu of its adjoint sweep -- three panel histories of its own,
@@ -107,17 +132,10 @@ struct qgd_handle_s {
         double *F = nullptr, *Y = nullptr, *mu = nullptr, *gB = nullptr, *scal = nullptr;
         double *sbar = nullptr, *pbar = nullptr, *map = nullptr, *ebar = nullptr, *planes = nullptr;
     } pb;
-    std::vector<void *> pullback_bufs;
-    std::vector<size_t> pullback_key;  // (nt, n_pcof, and the lengths of the five uploads) they were sized for; empty: none
     // qgd_eval_dense: the interpolated panels [1 + (points-1) refine][Np][2cp] of a resident grid or of the
     // longest window, and the weight table of qgd_k_interp.hip with its host copy (the upload reads it)
     double *dense_panels = nullptr, *dense_w = nullptr;
     std::vector<double> dense_w_host;
-    std::vector<void *> dense_bufs;
-    std::vector<size_t> dense_key;     // (time points, refine, panel size, m, bits of dt) they were made for; empty: none
-    std::vector<void *> forcing_bufs;  // eval_forward with a user forcing
-    double *fsc_forcing = nullptr;     // (in forcing_bufs) the same slab for k_forcing_terms
-    size_t forcing_key = 0;
     bool have_basis = false, have_tables = false;
     StoredSweep sweep;
     std::vector<int32_t> ncoef, poff;
@@ -156,13 +174,11 @@ struct qgd_handle_s {
     // are pinned: the copies then run at PCIe speed.
     struct HostReg { void *host; void *dev; size_t bytes; bool zeroed; };
     std::vector<HostReg> regs;
-    std::vector<void *> stage_bufs;
     double *stage_hist = nullptr, *stage_lam = nullptr, *stage_f = nullptr;
     // qgd_eval_states / qgd_eval_populations / qgd_eval_expectations: compact staging buffer [rows, slots, c], the caller's level
     // map and the planes of the caller's observables ([N, N, n_obs] real parts, then as many imaginary parts when there are
-    // any) on the device (all in stage_bufs, grown to the largest request so far)
-    double *stage_obs = nullptr, *obs_map = nullptr, *obs_planes = nullptr;
-    size_t stage_obs_len = 0, obs_map_len = 0, obs_planes_len = 0;
+    // any) on the device (all in POOL_STAGE, grown to the largest request so far)
+    Grown stage_obs, obs_map, obs_planes;
     // qgd_set_lambda_derivatives: the m derivative columns of lambda_history as the reference leaves them
     bool lambda_derivs = false;
     double *dlam = nullptr, *dlam_scratch = nullptr, *stage_lam_full = nullptr;
@@ -225,7 +241,7 @@ int fail(qgd_handle h, int code, const std::string &msg);
 
 
 template <typename T>
-int dev_alloc(qgd_handle h, std::vector<void *> &pool, T **p, size_t count)
+int dev_alloc(qgd_handle h, T **p, size_t count)
 {
     void *q = nullptr;
     hipError_t e = hipMalloc(&q, count * sizeof(T) + 64);
@@ -235,9 +251,16 @@ int dev_alloc(qgd_handle h, std::vector<void *> &pool, T **p, size_t count)
         return fail(h, e == hipErrorOutOfMemory ? QGD_ERR_MEMORY : QGD_ERR_NO_DEVICE,
                     std::string("hipMalloc of ") + std::to_string(count * sizeof(T)) + " bytes: " + hipGetErrorString(e));
     }
-    pool.push_back(q);
     *p = static_cast<T *>(q);
     return QGD_OK;
+}
+
+template <typename T>
+int dev_alloc(qgd_handle h, std::vector<void *> &pool, T **p, size_t count)
+{
+    const int rc = dev_alloc(h, p, count);
+    if (!rc) pool.push_back(*p);
+    return rc;
 }
 
 
@@ -381,15 +404,11 @@ RcclApi &rccl();
 enum ObserveKind { OBS_STATES, OBS_POPULATIONS, OBS_EXPECTATIONS };
 struct Observe { ObserveKind kind; int n_groups; double *out; int n_obs; bool obs_im; int refine = 0; };
 
-// A buffer plan: the device buffers of a keyed pool, each listed once -- where its pointer goes, its length in doubles, whether
-// this problem has it (else the pointer is set to NULL).  plan_bytes: what the plan asks for (without dev_alloc's pad);
-// plan_alloc: the pool anew from the plan, freed again when an allocation fails.
-struct Buf { double **slot; size_t count; bool on = true; };
-inline size_t plan_bytes(const std::vector<Buf> &plan) { size_t n = 0; for (const Buf &b : plan) n += b.on ? b.count : 0; return n * sizeof(double); }
-
 // qgd_host_alloc.cpp
 void free_pool(std::vector<void *> &pool);
-int plan_alloc(qgd_handle h, std::vector<void *> &pool, const std::vector<Buf> &plan);
+void pool_release(Pool &pool);
+int pool_ensure(qgd_handle h, Pool &pool, const KeyedPlan &p, const char *fit = nullptr, size_t extra = 0, const std::function<int()> &fill = {});
+int pool_add(qgd_handle h, Pool &pool, double **slot, size_t count, size_t *len = nullptr);
 void free_sensitivity_buffers(qgd_handle h);
 void drop_graph(qgd_handle h);
 int plan_windows(qgd_handle h, int chunks, int win);
@@ -398,7 +417,7 @@ int alloc_grid(qgd_handle h);
 // qgd_host_output.cpp
 qgd_handle_s::HostReg *find_reg(qgd_handle h, const void *p, size_t bytes);
 int finish_copies(qgd_handle h);
-int grow_stage(qgd_handle h, double **p, size_t *len, size_t need);
+int grow_stage(qgd_handle h, Grown &g, size_t need);
 int history_out(qgd_handle h, double *uv_history, int save = 1);
 int panels_out(qgd_handle h, const double *panels, double **stage, double *out, size_t J, int n_first);
 int lambda_history_out(qgd_handle h, double *out);

@@ -22,23 +22,53 @@ void free_pool(std::vector<void *> &pool)
 }
 
 
-int plan_alloc(qgd_handle h, std::vector<void *> &pool, const std::vector<Buf> &plan)
+void pool_release(Pool &pool)
 {
-    free_pool(pool);
-    for (const Buf &b : plan) {
-        *b.slot = nullptr;
-        const int rc = b.on ? dev_alloc(h, pool, b.slot, b.count) : QGD_OK;
-        if (rc) { free_pool(pool); return rc; }
-    }
-    return QGD_OK;
+    for (const Pool::Held &b : pool.held) { (void)hipFree(b.mem); *b.slot = nullptr; if (b.len) *b.len = 0; }
+    pool.held.clear(); pool.key.clear();
 }
 
 
-// the buffers of the forced gradient, the Hessian and the Hessian-vector product follow the grid and the control basis
+// one more buffer into the pool, in place of the one its slot holds now (if any)
+int pool_add(qgd_handle h, Pool &pool, double **slot, size_t count, size_t *len)
+{
+    auto it = std::find_if(pool.held.begin(), pool.held.end(), [slot](const Pool::Held &b) { return b.slot == slot; });
+    if (it != pool.held.end()) { (void)hipFree(it->mem); pool.held.erase(it); }
+    *slot = nullptr; if (len) *len = 0;
+    const int rc = dev_alloc(h, slot, count);
+    if (!rc) { pool.held.push_back({*slot, slot, len}); if (len) *len = count; }
+    return rc;
+}
+
+
+// The pool as p = (key, plan) asks for it.  Under that key already: kept as it is.  Else released (so that its old buffers count as
+// free memory) and made anew from the plan; `fit`: only if the plan's bytes and `extra` more fit the memory budget and the free
+// device memory, else QGD_ERR_MEMORY with `fit` as the message.  `fill`: what the new buffers hold before their first use; the
+// key is set once it succeeded, so a pool is never kept without its fills.
+int pool_ensure(qgd_handle h, Pool &pool, const KeyedPlan &p, const char *fit, size_t extra, const std::function<int()> &fill)
+{
+    if (pool.key == p.key) return QGD_OK;
+    pool_release(pool);
+    const size_t bytes = plan_bytes(p.plan) + extra;
+    size_t fr = 0, tot = 0;
+    if (fit && ((h->mem_budget && bytes > h->mem_budget) || (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr)))
+        return fail(h, QGD_ERR_MEMORY, std::string(fit) + " (" + std::to_string(bytes) + " bytes needed)");
+    int rc = QGD_OK;
+    for (const Buf &b : p.plan) {
+        *b.slot = nullptr;
+        if (!rc && b.on) rc = pool_add(h, pool, b.slot, b.count);
+    }
+    if (!rc && fill) rc = fill();
+    if (rc) pool_release(pool); else pool.key = p.key;
+    return rc;
+}
+
+
+// the sensitivity pools (forced gradient, Hessian, Hessian-vector product, pullback, dense output) follow the grid and the control basis
 void free_sensitivity_buffers(qgd_handle h)
 {
-    for (auto *pool : {&h->forced_bufs, &h->hess_bufs, &h->hvp_bufs, &h->pullback_bufs, &h->dense_bufs}) free_pool(*pool);
-    h->forced_key = h->hess_key = h->hvp_key = 0; h->pullback_key.clear(); h->dense_key.clear(); hvp_void(h);
+    for (int i = 0; i < N_SENS_POOLS; i++) pool_release(h->pools[i]);
+    hvp_void(h);
 }
 
 
@@ -202,10 +232,7 @@ int alloc_grid(qgd_handle h)
     h->grid_ready = false;
     free_pool(h->grid_bufs);
     free_sensitivity_buffers(h);
-    free_pool(h->forcing_bufs); h->forcing_key = 0;
-    free_pool(h->stage_bufs); h->stage_hist = h->stage_lam = h->stage_f = nullptr;
-    h->stage_obs = h->obs_map = h->obs_planes = nullptr; h->stage_obs_len = h->obs_map_len = h->obs_planes_len = 0;
-    h->dlam = h->dlam_scratch = h->stage_lam_full = nullptr;
+    pool_release(h->pools[POOL_FORCING]); pool_release(h->pools[POOL_STAGE]);
     h->chunk_state = h->carry_y = h->scal_scratch = nullptr; h->resident_window = 0;
     // ---- how much of the time grid is resident.  Everything (one window) when it fits the budget; else the grid is
     //      processed in `chunks` windows, one after the other in the same buffers (chunked_forward / chunked_adjoint).
@@ -542,8 +569,9 @@ void qgd_destroy(qgd_handle h)
     if (h->copy_stream2) { (void)hipStreamSynchronize(h->copy_stream2); (void)hipStreamDestroy(h->copy_stream2); }
     if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
     for (auto &r : h->regs) (void)hipHostUnregister(r.host);
-    free_pool(h->stage_bufs);
-    free_pool(h->static_bufs); free_pool(h->grid_bufs); free_pool(h->basis_bufs); free_pool(h->forced_bufs); free_pool(h->hess_bufs); free_pool(h->hvp_bufs); free_pool(h->pullback_bufs); free_pool(h->dense_bufs); free_pool(h->forcing_bufs);
+    pool_release(h->pools[POOL_STAGE]);      // (first, as ever: the order of the frees shapes the addresses later allocations get)
+    free_pool(h->static_bufs); free_pool(h->grid_bufs); free_pool(h->basis_bufs);
+    for (Pool &pool : h->pools) pool_release(pool);
     for (auto &p : h->phases) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     if (h->host_out) (void)hipHostFree(h->host_out);
     if (h->host_in) (void)hipHostFree(h->host_in);

@@ -502,9 +502,9 @@ int qgd_eval_populations(qgd_handle h, const double *pcof, int32_t n_pcof, int32
         return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
     if (level_map) {
         const size_t len = (size_t)n_groups * h->k.N;
-        int rc = grow_stage(h, &h->obs_map, &h->obs_map_len, len);
+        int rc = grow_stage(h, h->obs_map, len);
         if (rc) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->obs_map, level_map, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
+        HIP_TRY(h, hipMemcpyAsync(h->obs_map.p, level_map, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
     }
     return observe_eval(h, pcof, n_pcof, history_precomputed, Observe{OBS_POPULATIONS, level_map ? n_groups : 0, populations}, out3);
 }
@@ -522,10 +522,10 @@ int qgd_eval_expectations(qgd_handle h, const double *pcof, int32_t n_pcof, int3
     if (history_precomputed && h->sweep.kind == SWEEP_NONE)
         return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
     const size_t len = (size_t)n_obs * h->k.N * h->k.N;
-    int rc = grow_stage(h, &h->obs_planes, &h->obs_planes_len, (obs_im ? 2 : 1) * len);
+    int rc = grow_stage(h, h->obs_planes, (obs_im ? 2 : 1) * len);
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->obs_planes, obs_re, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
-    if (obs_im) HIP_TRY(h, hipMemcpyAsync(h->obs_planes + len, obs_im, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
+    HIP_TRY(h, hipMemcpyAsync(h->obs_planes.p, obs_re, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
+    if (obs_im) HIP_TRY(h, hipMemcpyAsync(h->obs_planes.p + len, obs_im, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
     return observe_eval(h, pcof, n_pcof, history_precomputed, Observe{OBS_EXPECTATIONS, 0, expect, n_obs, obs_im != nullptr}, out3);
 }
 
@@ -561,16 +561,16 @@ int qgd_eval_dense(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t his
         obs.kind = OBS_POPULATIONS;
         if (level_map) {
             const size_t len = (size_t)n_groups * k.N;
-            if ((rc = grow_stage(h, &h->obs_map, &h->obs_map_len, len))) return rc;
-            HIP_TRY(h, hipMemcpyAsync(h->obs_map, level_map, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
+            if ((rc = grow_stage(h, h->obs_map, len))) return rc;
+            HIP_TRY(h, hipMemcpyAsync(h->obs_map.p, level_map, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
             obs.n_groups = n_groups;
         }
     } else if (kind == QGD_DENSE_EXPECTATIONS) {
         obs.kind = OBS_EXPECTATIONS; obs.n_obs = n_obs; obs.obs_im = obs_im != nullptr;
         const size_t len = (size_t)n_obs * k.N * k.N;
-        if ((rc = grow_stage(h, &h->obs_planes, &h->obs_planes_len, (obs_im ? 2 : 1) * len))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->obs_planes, obs_re, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
-        if (obs_im) HIP_TRY(h, hipMemcpyAsync(h->obs_planes + len, obs_im, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
+        if ((rc = grow_stage(h, h->obs_planes, (obs_im ? 2 : 1) * len))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->obs_planes.p, obs_re, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
+        if (obs_im) HIP_TRY(h, hipMemcpyAsync(h->obs_planes.p + len, obs_im, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
     }
     return observe_eval(h, pcof, n_pcof, history_precomputed, obs, out3);
 }

@@ -108,27 +108,17 @@ static size_t stage_points(qgd_handle h)
 static int stage_alloc(qgd_handle h, double **stage, size_t doubles)
 {
     if (*stage) return QGD_OK;
-    int rc = dev_alloc(h, h->stage_bufs, stage, doubles);
+    int rc = pool_add(h, h->pools[POOL_STAGE], stage, doubles);
     if (rc) return rc;
     HIP_TRY(h, hipMemsetAsync(*stage, 0, doubles * sizeof(double), h->k.stream));
     return QGD_OK;
 }
 
 
-// a staging buffer of stage_bufs that grows to the largest request (the copies that read the old one were awaited by the
-// call that issued them)
-int grow_stage(qgd_handle h, double **p, size_t *len, size_t need)
+// a staging buffer that grows to the largest request (the copies that read the old one were awaited by the call that issued them)
+int grow_stage(qgd_handle h, Grown &g, size_t need)
 {
-    if (*p && *len >= need) return QGD_OK;
-    if (*p) {
-        auto it = std::find(h->stage_bufs.begin(), h->stage_bufs.end(), (void *)*p);
-        if (it != h->stage_bufs.end()) h->stage_bufs.erase(it);
-        (void)hipFree(*p);
-        *p = nullptr; *len = 0;
-    }
-    int rc = dev_alloc(h, h->stage_bufs, p, need);
-    if (!rc) *len = need;
-    return rc;
+    return g.p && g.len >= need ? QGD_OK : pool_add(h, h->pools[POOL_STAGE], &g.p, need, &g.len);
 }
 
 
@@ -217,10 +207,10 @@ int lambda_history_out(qgd_handle h, double *out)
     const size_t P = stage_points(h);
     int rc;
     if (!h->dlam) {
-        if ((rc = dev_alloc(h, h->stage_bufs, &h->dlam, P * std::max<size_t>(m, 1) * hstep))) return rc;
+        if ((rc = pool_add(h, h->pools[POOL_STAGE], &h->dlam, P * std::max<size_t>(m, 1) * hstep))) return rc;
         // (the 1+m work panels of k_adjoint_derivs: LDS up to 150 KB, else an HBM slab per workgroup)
         if ((m + 1) * (size_t)k.Np * 16 * sizeof(double) > 150 * 1024 &&
-            (rc = dev_alloc(h, h->stage_bufs, &h->dlam_scratch, (P - 1) * (size_t)(k.cp / 8) * (m + 1) * k.Np * 16))) return rc;
+            (rc = pool_add(h, h->pools[POOL_STAGE], &h->dlam_scratch, (P - 1) * (size_t)(k.cp / 8) * (m + 1) * k.Np * 16))) return rc;
     }
     if ((rc = stage_alloc(h, &h->stage_lam_full, sd * P * k.c))) return rc;
     { PhaseTimer t(h, "lambda_derivs"); K_TRY(h, qgdk_adjoint_derivs(&k, h->dlam, h->dlam_scratch)); }
@@ -253,29 +243,21 @@ static void dense_weights(std::vector<double> &w, int m, int r, double dt)
 
 
 // buffers of qgd_eval_dense (refine > 1): the interpolated panels of a resident grid, or of the longest window of a windowed
-// one, and the weight table.  Kept on the handle under a key, freed with the sensitivity buffers; QGD_ERR_MEMORY when they do
-// not fit the memory budget or the free device memory.  (One buffer, no slabs: 8 KB per sub-point at cnot3.)  The key holds all
-// that sizes or fills them: the points, refine, the panel size, m and dt.
+// one, and the weight table, in a sensitivity pool with a fit check.  (One buffer, no slabs: 8 KB per sub-point at cnot3.)  The
+// key holds all that sizes or fills them: the points, refine, the panel size, m and dt.
 int dense_buffers(qgd_handle h, int refine)
 {
     const qgdk_ctx &k = h->k;
     const size_t hstep = (size_t)k.Np * 2 * k.cp, P = stage_points(h), pts = 1 + (P - 1) * (size_t)refine;
     size_t dt_bits = 0;
     memcpy(&dt_bits, &k.dt, sizeof(double) < sizeof(size_t) ? sizeof(double) : sizeof(size_t));
-    const std::vector<size_t> key = {P, (size_t)refine, hstep, (size_t)k.m, dt_bits};
-    if (h->dense_key == key) return QGD_OK;
-    h->dense_key.clear();
-    free_pool(h->dense_bufs);
-    const std::vector<Buf> plan = {{&h->dense_panels, pts * hstep}, {&h->dense_w, (size_t)2 * (k.m + 1) * (refine - 1)}};
-    size_t bytes = plan_bytes(plan), fr = 0, tot = 0;
-    if ((h->mem_budget && bytes > h->mem_budget) || (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr))
-        return fail(h, QGD_ERR_MEMORY, "the interpolated panels of qgd_eval_dense do not fit (" + std::to_string(bytes) + " bytes needed)");
-    int rc = plan_alloc(h, h->dense_bufs, plan);
-    if (rc) return rc;
-    dense_weights(h->dense_w_host, k.m, refine, k.dt);
-    HIP_TRY(h, hipMemcpyAsync(h->dense_w, h->dense_w_host.data(), h->dense_w_host.size() * sizeof(double), hipMemcpyHostToDevice, k.stream));
-    h->dense_key = key;
-    return QGD_OK;
+    return pool_ensure(h, h->pools[POOL_DENSE], {{P, (size_t)refine, hstep, (size_t)k.m, dt_bits},
+                       {{&h->dense_panels, pts * hstep}, {&h->dense_w, (size_t)2 * (k.m + 1) * (refine - 1)}}},
+                       "the interpolated panels of qgd_eval_dense do not fit", 0, [&]() -> int {
+        dense_weights(h->dense_w_host, k.m, refine, k.dt);
+        HIP_TRY(h, hipMemcpyAsync(h->dense_w, h->dense_w_host.data(), h->dense_w_host.size() * sizeof(double), hipMemcpyHostToDevice, k.stream));
+        return QGD_OK;
+    });
 }
 
 
@@ -305,20 +287,20 @@ int observe_out(qgd_handle h, const Observe &obs, int save)
         K_TRY(h, qgdk_interp(&k, k.hist, k.dpsi, h->dense_panels, obs.refine, h->dense_w, k.stream));
         panels = h->dense_panels;
     }
-    if ((rc = grow_stage(h, &h->stage_obs, &h->stage_obs_len, rows * sp.count * k.c))) return rc;
+    if ((rc = grow_stage(h, h->stage_obs, rows * sp.count * k.c))) return rc;
     const double *src = panels + sp.first * hstep;
     if (obs.kind == OBS_STATES) {
-        K_TRY(h, qgdk_layout(&k, src, (long long)(hstep * sp.stride), 0, h->stage_obs, (long long)(sp.count * rows), (long long)rows, 0, 0, (int)sp.count, 1, 0, k.stream, 0));
+        K_TRY(h, qgdk_layout(&k, src, (long long)(hstep * sp.stride), 0, h->stage_obs.p, (long long)(sp.count * rows), (long long)rows, 0, 0, (int)sp.count, 1, 0, k.stream, 0));
     } else if (obs.kind == OBS_EXPECTATIONS) {
         PhaseTimer t(h, "expectations");
-        K_TRY(h, qgdk_expectations(&k, src, (long long)(hstep * sp.stride), h->stage_obs, (long long)(sp.count * rows), (long long)rows, (int)sp.count,
-                                   h->obs_planes, obs.obs_im ? h->obs_planes + (size_t)obs.n_obs * k.N * k.N : nullptr, obs.n_obs, k.stream));
+        K_TRY(h, qgdk_expectations(&k, src, (long long)(hstep * sp.stride), h->stage_obs.p, (long long)(sp.count * rows), (long long)rows, (int)sp.count,
+                                   h->obs_planes.p, obs.obs_im ? h->obs_planes.p + (size_t)obs.n_obs * k.N * k.N : nullptr, obs.n_obs, k.stream));
     } else {
         PhaseTimer t(h, "populations");
-        K_TRY(h, qgdk_populations(&k, src, (long long)(hstep * sp.stride), h->stage_obs, (long long)(sp.count * rows), (long long)rows, (int)sp.count,
-                                  obs.n_groups > 0 ? h->obs_map : nullptr, obs.n_groups, k.stream));
+        K_TRY(h, qgdk_populations(&k, src, (long long)(hstep * sp.stride), h->stage_obs.p, (long long)(sp.count * rows), (long long)rows, (int)sp.count,
+                                  obs.n_groups > 0 ? h->obs_map.p : nullptr, obs.n_groups, k.stream));
     }
-    return send_staged(h, h->stage_obs, rows, 0, sp, obs.out, rows);
+    return send_staged(h, h->stage_obs.p, rows, 0, sp, obs.out, rows);
 }
 
 }  // namespace qgdh

@@ -6,43 +6,29 @@
 
 using namespace qgdh;
 
-// buffers of the forced gradient for (up to) nt time points and B scan blocks.  With `bytes`: nothing is allocated, the bytes
-// a call without it would allocate are added to *bytes (0 when the buffers are there already).
-static int forced_buffers(qgd_handle h, size_t nt, size_t B, size_t *bytes = nullptr)
+// the forced gradient's pool for (up to) nt time points and B scan blocks: its key and its plan
+static KeyedPlan forced_plan(qgd_handle h, size_t nt, size_t B)
 {
     qgdk_ctx &k = h->k;
     const size_t hstep = (size_t)k.Np * 2 * k.cp, NB = (size_t)k.n_ops * 2 * k.m;
     const size_t cpS = (size_t)k.n_pcof * k.cp, hstepS = (size_t)k.Np * 2 * cpS;
-    const size_t key = (nt * 1000003u + (size_t)k.n_pcof) * 4099u + B;
-    if (h->forced_key != key) {
-        const std::vector<Buf> plan = {
-            {&k.fs_BR, nt * NB * hstep}, {&k.fs_BL, nt * NB * hstep}, {&k.fs_phi, B * hstepS}, {&k.fs_bnd, (B + 1) * hstepS},
-            {&k.fs_gacc, (size_t)k.n_pcof + 1},
-            // (the 2m+2 work panels of k_forced_basis: LDS up to 150 KB, else an HBM slab per workgroup)
-            {&h->fsc_forced, nt * (size_t)(k.cp / 8) * (size_t)(2 * k.m + 2) * k.Np * 16, qgdk_forced_lds(k.Np, k.m) > 150 * 1024}};
-        if (bytes) { *bytes += plan_bytes(plan); return QGD_OK; }
-        h->forced_key = 0;
-        int rc = plan_alloc(h, h->forced_bufs, plan);
-        if (rc) return rc;
-        h->forced_key = key;
-    }
-    if (!bytes) k.fs_scratch = h->fsc_forced;
-    return QGD_OK;
+    return {{nt, (size_t)k.n_pcof, B}, {
+        {&k.fs_BR, nt * NB * hstep}, {&k.fs_BL, nt * NB * hstep}, {&k.fs_phi, B * hstepS}, {&k.fs_bnd, (B + 1) * hstepS},
+        {&k.fs_gacc, (size_t)k.n_pcof + 1},
+        // (the 2m+2 work panels of k_forced_basis: LDS up to 150 KB, else an HBM slab per workgroup)
+        {&h->fsc_forced, nt * (size_t)(k.cp / 8) * (size_t)(2 * k.m + 2) * k.Np * 16, qgdk_forced_lds(k.Np, k.m) > 150 * 1024}}};
 }
 
-
-// The pool of a second-order entry point, anew from its plan.  QGD_ERR_MEMORY is decided from what THIS call allocates: the plan
-// and, when they are not there under the right key, the forced gradient's buffers (with_forced: the entry point needs them).
-static int second_order_alloc(qgd_handle h, std::vector<void *> &pool, const std::vector<Buf> &plan, const std::string &what,
-                              bool with_forced = true)
+static int forced_buffers(qgd_handle h, size_t nt, size_t B)
 {
-    free_pool(pool);
-    size_t bytes = plan_bytes(plan), fr = 0, tot = 0;
-    if (with_forced) (void)forced_buffers(h, (size_t)h->k.nt, (size_t)h->k.scan_blocks, &bytes);
-    if ((h->mem_budget && bytes > h->mem_budget) || (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr))
-        return fail(h, QGD_ERR_MEMORY, what + " (" + std::to_string(bytes) + " bytes needed)");
-    return plan_alloc(h, pool, plan);
+    const int rc = pool_ensure(h, h->pools[POOL_FORCED], forced_plan(h, nt, B));
+    if (!rc) h->k.fs_scratch = h->fsc_forced;
+    return rc;
 }
+
+// QGD_ERR_MEMORY of a second-order entry point is decided from what ITS call allocates: its own plan and, when they are not there
+// under the right key, the forced gradient's buffers -- these bytes
+static size_t forced_missing(qgd_handle h) { return pool_missing(h->pools[POOL_FORCED], forced_plan(h, (size_t)h->k.nt, (size_t)h->k.scan_blocks)); }
 
 
 // how both second-order entry points begin, and what they refuse (`name`: the entry point, `what`: its result, for the messages)
@@ -147,18 +133,12 @@ static int hess_buffers(qgd_handle h)
     qgdk_ctx &k = h->k;
     const size_t nt = k.nt, np = (size_t)k.n_pcof, NB = (size_t)k.n_ops * 2 * k.m, gpc = (size_t)k.cp / 8;
     const size_t hstep = (size_t)k.Np * 2 * k.cp, n_shist = nt * (size_t)k.Np * 2 * np * k.cp, n_ws = k.have_guard == 1 ? n_shist : 0;
-    const size_t key = ((nt * 1000003u + np) * 4099u + NB) * 2u + (n_ws ? 1u : 0u);
-    if (h->hess_key == key) return QGD_OK;
     auto &b = h->hs;
-    h->hess_key = 0;
-    int rc = second_order_alloc(h, h->hess_bufs, {
+    return pool_ensure(h, h->pools[POOL_HESS], {{nt, np, NB, (size_t)(n_ws != 0)}, {
         {&b.shist, n_shist}, {&b.ws, n_ws, n_ws != 0}, {&b.Z, nt * NB * hstep}, {&b.half, nt * gpc * NB * NB},
         {&b.slab, nt * gpc * qgdk_hess_slab(k.Np, k.m, k.n_ops)}, {&b.zt, nt * NB * np},
-        {&b.Y, 2 * np * np + (k.have_guard ? qgdk_hess_gram_part((int)np, (int)nt) : 0)}},
-        "the sensitivity history of qgd_eval_hessian does not fit");
-    if (rc) return rc;
-    h->hess_key = key;
-    return QGD_OK;
+        {&b.Y, 2 * np * np + (k.have_guard ? qgdk_hess_gram_part((int)np, (int)nt) : 0)}}},
+        "the sensitivity history of qgd_eval_hessian does not fit", forced_missing(h));
 }
 
 
@@ -169,31 +149,27 @@ static int hvp_buffers(qgd_handle h)
     qgdk_ctx &k = h->k;
     const size_t nt = k.nt, np = (size_t)k.n_pcof, NB = (size_t)k.n_ops * 2 * k.m, gpc = (size_t)k.cp / 8, B = (size_t)k.scan_blocks;
     const size_t hstep = (size_t)k.Np * 2 * k.cp, hist = nt * hstep, n_ws = k.have_guard == 1 ? hist : 0, n_gv = qgdk_hvp_gv_len(&k);
-    const size_t key = ((((nt * 1000003u + np) * 4099u + NB) * 2u + (n_ws ? 1u : 0u)) * 1031u + B) | 1u;
-    if (h->hvp_key == key) return QGD_OK;
+    const std::vector<size_t> key = {nt, np, NB, (size_t)(n_ws != 0), B};
+    if (h->pools[POOL_HVP].key != key) hvp_void(h);
     auto &b = h->hv;
-    double *one3 = nullptr;
-    h->hvp_key = 0; hvp_void(h);
-    int rc = second_order_alloc(h, h->hvp_bufs, {
+    return pool_ensure(h, h->pools[POOL_HVP], {key, {
         {&b.Z, nt * NB * hstep}, {&b.half, nt * gpc * NB * NB}, {&b.slab, nt * gpc * qgdk_hess_slab(k.Np, k.m, k.n_ops)},
         {&b.sv, hist}, {&b.F, hist}, {&b.Y, hist}, {&b.mu, hist}, {&b.ws, n_ws, n_ws != 0}, {&b.phi, B * hstep},
         {&b.bnd, (B + 1) * hstep}, {&b.gvt, n_gv}, {&b.term, hstep}, {&b.part, nt * gpc * NB}, {&b.v, np}, {&b.gB, np},
-        {&b.out, np}, {&b.scal, 4}, {&one3, 2}},
-        "the buffers of qgd_eval_hessian_vec do not fit");
-    if (rc) return rc;
-    b.one3 = one3;
-    // s_v(0) = 0 and mu_0 = 0 are never written again; the unused (M+1)-th Taylor slot of the direction table stays zero
-    const struct { int64_t goff; int32_t ncoef, poff; } one = {0, 1, 0};      // the one-operator, one-coefficient basis of the direction table
-    HIP_TRY(h, hipMemcpyAsync(one3, &one, sizeof(one), hipMemcpyHostToDevice, k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.sv, 0, hist * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.mu, 0, hist * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.Y, 0, hist * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.bnd, 0, (B + 1) * hstep * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.gvt, 0, n_gv * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.scal, 0, 4 * sizeof(double), k.stream));
-    HIP_TRY(h, hipStreamSynchronize(k.stream));      // (`one` leaves scope)
-    h->hvp_key = key;
-    return QGD_OK;
+        {&b.out, np}, {&b.scal, 4}, {&b.one3, 2}}},
+        "the buffers of qgd_eval_hessian_vec do not fit", forced_missing(h), [&]() -> int {
+        // s_v(0) = 0 and mu_0 = 0 are never written again; the unused (M+1)-th Taylor slot of the direction table stays zero
+        const struct { int64_t goff; int32_t ncoef, poff; } one = {0, 1, 0};      // the one-operator, one-coefficient basis of the direction table
+        HIP_TRY(h, hipMemcpyAsync(b.one3, &one, sizeof(one), hipMemcpyHostToDevice, k.stream));
+        HIP_TRY(h, hipMemsetAsync(b.sv, 0, hist * sizeof(double), k.stream));
+        HIP_TRY(h, hipMemsetAsync(b.mu, 0, hist * sizeof(double), k.stream));
+        HIP_TRY(h, hipMemsetAsync(b.Y, 0, hist * sizeof(double), k.stream));
+        HIP_TRY(h, hipMemsetAsync(b.bnd, 0, (B + 1) * hstep * sizeof(double), k.stream));
+        HIP_TRY(h, hipMemsetAsync(b.gvt, 0, n_gv * sizeof(double), k.stream));
+        HIP_TRY(h, hipMemsetAsync(b.scal, 0, 4 * sizeof(double), k.stream));
+        HIP_TRY(h, hipStreamSynchronize(k.stream));      // (`one` leaves scope)
+        return QGD_OK;
+    });
 }
 
 
@@ -233,21 +209,28 @@ static int pullback_buffers(qgd_handle h, size_t n_sbar, size_t n_pbar, size_t n
 {
     qgdk_ctx &k = h->k;
     const size_t hist = (size_t)k.nt * k.Np * 2 * k.cp, np = (size_t)k.n_pcof;
-    const std::vector<size_t> key = {(size_t)k.nt, np, n_sbar, n_pbar, n_map, n_ebar, n_planes};
-    if (h->pullback_key == key) return QGD_OK;
     auto &b = h->pb;
-    h->pullback_key.clear();
-    int rc = second_order_alloc(h, h->pullback_bufs, {
+    return pool_ensure(h, h->pools[POOL_PULLBACK], {{(size_t)k.nt, np, n_sbar, n_pbar, n_map, n_ebar, n_planes}, {
         {&b.F, hist}, {&b.Y, hist}, {&b.mu, hist}, {&b.gB, np}, {&b.scal, 4}, {&b.sbar, n_sbar, n_sbar != 0}, {&b.pbar, n_pbar, n_pbar != 0},
-        {&b.map, n_map, n_map != 0}, {&b.ebar, n_ebar, n_ebar != 0}, {&b.planes, n_planes, n_planes != 0}},
-        "the buffers of qgd_eval_pullback do not fit", false);
-    if (rc) return rc;
-    // mu_0 and y_0 are never written; the forcing kernel writes every panel of F on every call
-    HIP_TRY(h, hipMemsetAsync(b.mu, 0, hist * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.Y, 0, hist * sizeof(double), k.stream));
-    HIP_TRY(h, hipMemsetAsync(b.scal, 0, 4 * sizeof(double), k.stream));
-    h->pullback_key = key;
-    return QGD_OK;
+        {&b.map, n_map, n_map != 0}, {&b.ebar, n_ebar, n_ebar != 0}, {&b.planes, n_planes, n_planes != 0}}},
+        "the buffers of qgd_eval_pullback do not fit", 0, [&]() -> int {
+        // mu_0 and y_0 are never written; the forcing kernel writes every panel of F on every call
+        HIP_TRY(h, hipMemsetAsync(b.mu, 0, hist * sizeof(double), k.stream));
+        HIP_TRY(h, hipMemsetAsync(b.Y, 0, hist * sizeof(double), k.stream));
+        HIP_TRY(h, hipMemsetAsync(b.scal, 0, 4 * sizeof(double), k.stream));
+        return QGD_OK;
+    });
+}
+
+
+// The context of a second-order adjoint sweep: a copy of the handle's with the sweep's forcing, y, mu, gradient and scalars in
+// buffers of its own, so that lambda, the guard forcing and the scalars of the kept evaluation stay as they are
+static qgdk_ctx adjoint_context(const qgdk_ctx &k, double *F, double *Y, double *mu, double *gB, double *scal)
+{
+    qgdk_ctx a = k;
+    a.forcing = F; a.yhist = Y; a.lam = mu; a.grad = gB; a.scal = scal;
+    a.front = 0; a.fuse_terminal = 0; a.grad_accumulate = 0; a.mirror_dev = nullptr; a.mirror_ticket = nullptr;
+    return a;
 }
 
 
@@ -361,11 +344,7 @@ int qgd_eval_hessian_vec(qgd_handle h, const double *pcof, int32_t n_pcof, const
         HIP_TRY(h, hipStreamSynchronize(k.stream));
         h->hvp_valid = true;
     }
-    // the second-order adjoint runs on a copy of the context: its forcing, y and mu in the product's own buffers, so that
-    // lambda, the guard forcing and the scalars of the kept evaluation stay as they are for the next vector
-    qgdk_ctx a = k;
-    a.forcing = b.F; a.yhist = b.Y; a.lam = b.mu; a.grad = b.gB; a.scal = b.scal;
-    a.front = 0; a.fuse_terminal = 0; a.grad_accumulate = 0; a.mirror_dev = nullptr; a.mirror_ticket = nullptr;
+    const qgdk_ctx a = adjoint_context(k, b.F, b.Y, b.mu, b.gB, b.scal);      // (the same for every vector)
     for (int32_t j = 0; j < n_vec; j++) {
         HIP_TRY(h, hipMemcpyAsync(b.v, v + (size_t)j * np, np * sizeof(double), hipMemcpyHostToDevice, k.stream));
         { PhaseTimer t(h, "hvp_direction"); K_TRY(h, qgdk_hvp_gv(&k, b.v, b.gvt)); }
@@ -429,10 +408,7 @@ int qgd_eval_pullback(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t 
     if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
     { PhaseTimer t(h, "pullback_forcing");
       K_TRY(h, qgdk_pullback_forcing(&k, b.F, save, b.sbar, b.pbar, b.map, n_groups, b.ebar, b.planes, with_im ? b.planes + n_plane : nullptr, n_obs)); }
-    // (as the second-order adjoint of qgd_eval_hessian_vec: lambda, the guard forcing and the scalars of the stored evaluation stay)
-    qgdk_ctx a = k;
-    a.forcing = b.F; a.yhist = b.Y; a.lam = b.mu; a.grad = b.gB; a.scal = b.scal;
-    a.front = 0; a.fuse_terminal = 0; a.grad_accumulate = 0; a.mirror_dev = nullptr; a.mirror_ticket = nullptr;
+    const qgdk_ctx a = adjoint_context(k, b.F, b.Y, b.mu, b.gB, b.scal);
     { PhaseTimer t(h, "pullback_adjoint"); K_TRY(h, qgdk_hvp_adjoint(&a)); }
     { PhaseTimer t(h, "pullback_gradient"); K_TRY(h, qgdk_gradient(&a)); }
     if ((rc = check_status(h))) return rc;

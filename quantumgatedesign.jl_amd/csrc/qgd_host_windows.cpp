@@ -138,19 +138,13 @@ int forcing_buffers(qgd_handle h, size_t nt, size_t B)
 {
     qgdk_ctx &k = h->k;
     const size_t m = k.m, hstep = (size_t)k.Np * 2 * k.cp;
-    const size_t key = nt * 4099u + B;
-    if (h->forcing_key != key) {
-        h->forcing_key = 0;
-        const int rc = plan_alloc(h, h->forcing_bufs, {
-            {&k.ff_F, nt * m * hstep}, {&k.ff_E, nt * m * hstep}, {&k.ff_XR, nt * hstep}, {&k.ff_XL, nt * hstep}, {&k.ff_Q, nt * hstep},
-            {&k.ff_phi, (B + 1) * hstep}, {&k.ff_bnd, (B + 2) * hstep},
-            // (N > 64 at high order: the m+2 work panels of k_forcing_terms do not fit in LDS)
-            {&h->fsc_forcing, nt * (size_t)(k.cp / 8) * (m + 2) * k.Np * 16, (size_t)(m + 2) * k.Np * 16 * sizeof(double) > 150 * 1024}});
-        if (rc) return rc;
-        h->forcing_key = key;
-    }
-    k.fs_scratch = h->fsc_forcing;
-    return QGD_OK;
+    const int rc = pool_ensure(h, h->pools[POOL_FORCING], {{nt, B}, {
+        {&k.ff_F, nt * m * hstep}, {&k.ff_E, nt * m * hstep}, {&k.ff_XR, nt * hstep}, {&k.ff_XL, nt * hstep}, {&k.ff_Q, nt * hstep},
+        {&k.ff_phi, (B + 1) * hstep}, {&k.ff_bnd, (B + 2) * hstep},
+        // (N > 64 at high order: the m+2 work panels of k_forcing_terms do not fit in LDS)
+        {&h->fsc_forcing, nt * (size_t)(k.cp / 8) * (m + 2) * k.Np * 16, (size_t)(m + 2) * k.Np * 16 * sizeof(double) > 150 * 1024}}});
+    if (!rc) k.fs_scratch = h->fsc_forcing;
+    return rc;
 }
 
 
