@@ -300,6 +300,33 @@ int qgd_apply_hamiltonian(qgd_handle h, int32_t time_index, int32_t deriv_order,
  * handle (QGD_TINY=0 in the environment: for every handle). */
 int qgd_set_small_path(qgd_handle h, int32_t on);
 
+/* A batch of evaluations: n_members coefficient vectors pcofs[n_members][n_pcof] (row-major) of the handle's problem in one
+ * call.  Member k receives exactly what the matching single call on this handle returns for pcofs + k * n_pcof, bit for bit:
+ * qgd_discrete_adjoint (no history arrays) when grads != NULL, qgd_eval_forward when it is NULL -- the gradient into
+ * grads[k][n_pcof], the three scalars of those calls into out3[k][3], under the handle's current cost type, target and guard
+ * projector.  member_status (NULL, or [n_members]): 1 where a step matrix of that member was singular, else 0.
+ *
+ * Where the small-problem path of qgd_set_small_path would take the single call, the members of a chunk (at most 1024 of
+ * them, fewer when the memory budget or the free device memory holds fewer; larger batches run chunk after chunk inside the
+ * call) run side by side: one upload, four launches and one download per chunk (about
+ * nt * (tables row + 128 + n_pcof) + 8 doubles of device memory per member, counted against qgd_set_memory_budget).
+ * Everywhere else -- N > 4, windowed grids, n_pcof > 64, the path switched off, event bracketing -- the library runs the
+ * single evaluations one after another.  qgd_get_intermediate "batch_path" tells which it was.
+ *
+ * A batch leaves no stored sweep: a later history_precomputed call is refused as after qgd_create, on both routes.
+ *
+ * Refused before anything is launched, the handle's state as it was:
+ *   QGD_ERR_ARGUMENT     pcofs or out3 NULL, n_members < 1, n_pcof different from the control basis's
+ *   QGD_ERR_STATE        no control basis; grads given without a target
+ *   QGD_ERR_UNSUPPORTED  a handle with a communicator or a partition
+ *   QGD_ERR_MEMORY       not even one member's arrays fit the memory budget or the free device memory
+ * QGD_ERR_NUMERIC: a step matrix of some member was singular.  The other members' results are written all the same,
+ * member_status names the singular ones; what a singular member's own row of grads and out3 holds is unspecified. */
+int qgd_eval_batch(qgd_handle h, const double *pcofs, int32_t n_members, int32_t n_pcof,
+                   double *grads,          /* [n_members][n_pcof] row-major, or NULL: forward evaluations only */
+                   double *out3,           /* [n_members][3]: the three scalars of qgd_discrete_adjoint / qgd_eval_forward */
+                   int32_t *member_status  /* [n_members] or NULL: 1 where a step matrix of that member was singular */);
+
 /* Diagnostics: copy a named intermediate of the last evaluation to the host.
  * Names: "L", "R", "Linv", "P" (complex, returned as [nt][N][N][2] C-order),
  * "sigma" ([nt][n_ops][m][2]), "tables" ([nt][m][n_ops][2]), "repivoted" (1 value: how many step matrices of the last
@@ -309,7 +336,8 @@ int qgd_set_small_path(qgd_handle h, int32_t on);
  * "selection" (4 values: operator path -- 2 sparse ELL kernels, 1 the N > 64 GEMM-style kernels, 0 dense N <= 64 --,
  * form of the gradient scalars on the N > 64 path 0..3 or -1, block Gauss-Jordan inverse in use 0/1, windows of the time
  * grid), "small_path" (1 value: whether the last evaluation ran on the small-problem path of qgd_set_small_path), "front_path"
- * (1 value: whether the last forward evaluation took the fused front, below).  Returns the number of doubles the buffer needs
+ * (1 value: whether the last forward evaluation took the fused front, below), "batch_path" (1 value: whether the last
+ * qgd_eval_batch call ran its members side by side, 1, or one after another, 0).  Returns the number of doubles the buffer needs
  * through *needed when out == NULL.
  *
  * The fused front (N = 64 with sparse operators, Hermite order <= 8, 513 .. 704 time points, one rank, the grid resident, a

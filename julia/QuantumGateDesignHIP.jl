@@ -453,6 +453,36 @@ function hip_eval_grad_forced(prob::SchrodingerProb, controls, pcof::Vector{Floa
     return grad
 end
 
+"""
+    hip_eval_batch(prob, controls, pcofs, target; order=2, cost_type=:Infidelity, gradient=true)
+
+Many coefficient vectors of one problem in one device call (qgd_eval_batch): `pcofs` is `[n_pcof, K]`, one member per COLUMN
+(the C ABI's row-major `[K][n_pcof]` as Julia stores it).  Returns `(grads [n_pcof, K] or nothing, scalars [3, K], status [K])`:
+column `k` is what hip_discrete_adjoint! (`gradient=false`: the forward evaluation) gives for `pcofs[:, k]`, bit for bit;
+`status[k] = 1` where a step matrix of member `k` was singular (the other members are valid: no error is thrown for that alone).
+What the reference does with `Threads.@threads` over evaluations (examples/optimization_with_random_pcof.jl).  Controls linear
+in pcof.  Like the rest of this file, not run in this repository.
+"""
+function hip_eval_batch(prob::SchrodingerProb, controls, pcofs::Matrix{Float64}, target::AbstractMatrix{<:Number};
+        order::Int=2, cost_type=:Infidelity, gradient::Bool=true)
+    n_pcof, K = size(pcofs)
+    K >= 1 || throw(ArgumentError("pcofs holds no member"))
+    n_pcof == get_number_of_control_parameters(controls) || throw(DimensionMismatch("pcofs must be [n_pcof, K]"))
+    dp = device_problem(prob, order)
+    set_controls!(dp, prob, controls, pcofs[:, 1])
+    dp.general && throw(ArgumentError("hip_eval_batch needs controls that are linear in pcof"))
+    set_cost_type!(dp, cost_type)
+    tr = Matrix{Float64}(vcat(real(target), imag(target)))
+    check(dp.handle, ccall((:qgd_set_target, libqgd), Cint, (Ptr{Cvoid}, Ptr{Float64}), dp.handle, tr))
+    grads = gradient ? zeros(n_pcof, K) : nothing
+    scalars, status = zeros(3, K), zeros(Int32, K)
+    rc = GC.@preserve pcofs grads ccall((:qgd_eval_batch, libqgd), Cint,
+          (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+          dp.handle, pcofs, K, n_pcof, gradient ? pointer(grads) : Ptr{Float64}(C_NULL), scalars, status)
+    rc == 5 || check(dp.handle, rc)        # (QGD_ERR_NUMERIC: `status` names the singular members)
+    return grads, scalars, status
+end
+
 # eval_hessian(prob, controls, pcof, target; order) (src/eval_hessian.jl): the exact Hessian of the discrete objective on the
 # device (controls linear in pcof), n_pcof x n_pcof.
 function hip_eval_hessian(prob::SchrodingerProb, controls, pcof::Vector{Float64},

@@ -191,6 +191,14 @@ int qgdk_adjoint_derivs(const qgdk_ctx *c, double *dlam, double *scratch);
 int qgdk_tiny_supported(const qgdk_ctx *c, int n_pcof);      // small problems (N <= 4): four launches instead of twelve (qgd_k_tiny.hip)
 int qgdk_tiny_eval(const qgdk_ctx *c, const double *pcof_host, int n_pcof, int gradient);
 int qgdk_contract_rows(const qgdk_ctx *c, int rows);         // cpart rows -> grad (+ host mirror), fixed order
+// a batch of small-problem evaluations (qgd_eval_batch): the device arrays of its members, one member stride apart each
+// (qgdk_tiny_batch_layout: tab, each of Rg / Linv / psi / lam, cpart; small: QGD_TINY_BATCH_SMALL doubles, scal(4) then the
+// status word), the coefficients pcofs[members][n_pcof] and the result rows[members][n_pcof + 5]
+#define QGD_TINY_BATCH_SMALL 8
+typedef struct { const double *pcofs; double *tab, *Rg, *Linv, *psi, *lam, *cpart, *small, *rows; } qgdk_tiny_batch;
+void qgdk_tiny_batch_layout(const qgdk_ctx *c, int n_pcof, size_t *tab, size_t *mat, size_t *cpart);
+int qgdk_tiny_eval_batch(const qgdk_ctx *c, const qgdk_tiny_batch *b, int members, int n_pcof, int gradient);
+int qgdk_contract_rows_batch(const qgdk_ctx *c, const qgdk_tiny_batch *b, int members, int n_pcof, int rows);
 int qgdk_mirror_scalars(const qgdk_ctx *c);      // result mirror of an evaluation without a gradient: [scal | status | sequence number]
 size_t qgdk_lds_needed(int Np, int m, int n_ops);
 int qgdk_sparse_supported(int Np, int m, int n_ops, int Z);

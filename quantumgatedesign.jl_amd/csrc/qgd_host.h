@@ -62,6 +62,7 @@ using qgdh::Phase;
 //   on a resident grid nothing is re-run, and a NULL-pcof history_precomputed call after new tables reuses the sweep -- the
 //   caller's promise that the history belongs to them, as in the reference.
 // A call that is refused before its first launch leaves the record as it was.
+// A batch (qgd_eval_batch) ends at SWEEP_NONE on both of its routes: no later history_precomputed call may refer to a batch.
 enum SweepKind { SWEEP_NONE, SWEEP_GENERAL, SWEEP_FRONT, SWEEP_SMALL };
 struct StoredSweep {
     SweepKind kind = SWEEP_NONE;
@@ -79,6 +80,7 @@ struct StoredSweep {
 // a grow-to-largest buffer's pointer, Grown) and the exact tuple they were made for (empty: nothing allocated under a key).
 // pool_release frees them, writes NULL (and length 0) into every slot and clears the key; pool_missing: the bytes pool_ensure
 // would allocate for a (key, plan) pair.  The other functions are in qgd_host_alloc.cpp.
+#define QGD_BATCH_CHUNK_MAX 1024      // members of a batch that share one set of launches (qgd_eval_batch)
 struct Buf { double **slot; size_t count; bool on = true; };
 inline size_t plan_bytes(const std::vector<Buf> &plan) { size_t n = 0; for (const Buf &b : plan) n += b.on ? b.count : 0; return n * sizeof(double); }
 struct Grown { double *p = nullptr; size_t len = 0; };
@@ -89,7 +91,7 @@ struct Pool {
 };
 struct KeyedPlan { std::vector<size_t> key; std::vector<Buf> plan; };
 inline size_t pool_missing(const Pool &pool, const KeyedPlan &p) { return pool.key == p.key ? 0 : plan_bytes(p.plan); }
-enum { POOL_FORCED, POOL_HESS, POOL_HVP, POOL_PULLBACK, POOL_DENSE, N_SENS_POOLS, POOL_FORCING = N_SENS_POOLS, POOL_STAGE, N_POOLS };
+enum { POOL_FORCED, POOL_HESS, POOL_HVP, POOL_PULLBACK, POOL_DENSE, POOL_BATCH, N_SENS_POOLS, POOL_FORCING = N_SENS_POOLS, POOL_STAGE, N_POOLS };
 
 struct qgd_handle_s {
     qgdk_ctx k{};
@@ -108,6 +110,7 @@ struct qgd_handle_s {
     //   POOL_HVP       qgd_eval_hessian_vec (hv); that key and the scan blocks
     //   POOL_PULLBACK  qgd_eval_pullback (pb); key (nt, n_pcof, the lengths of the five uploads)
     //   POOL_DENSE     qgd_eval_dense (dense_panels, dense_w); key (time points, refine, panel size, m, bits of dt)
+    //   POOL_BATCH     qgd_eval_batch on the small-problem path (bt): the arrays of a chunk's members; key (chunk members, nt, m, n_ops, n_pcof)
     //   POOL_FORCING   qgd_eval_forward with a user forcing (k.ff_*, fsc_forcing); key (nt, scan blocks)
     //   POOL_STAGE     the staging buffers of the reference-layout outputs: no key, each made or grown on first need
     Pool pools[N_POOLS];
@@ -135,6 +138,14 @@ struct qgd_handle_s {
     // qgd_eval_dense: the interpolated panels [1 + (points-1) refine][Np][2cp] of a resident grid or of the
     // longest window, and the weight table of qgd_k_interp.hip with its host copy (the upload reads it)
     double *dense_panels = nullptr, *dense_w = nullptr;
+    // qgd_eval_batch: per member of a chunk the small-problem path's compact arrays, its scalars and
+    // status word, its coefficients and its result row; the pinned staging buffer [pcofs | rows] of one chunk; the largest chunk
+    // (QGD_BATCH_CHUNK, read when the handle is created: the tests force small chunks with it); the route of the last batch
+    struct BatchBufs { double *pcofs = nullptr, *tab = nullptr, *Rg = nullptr, *Linv = nullptr, *psi = nullptr, *lam = nullptr, *cpart = nullptr, *small = nullptr, *rows = nullptr; } bt;
+    double *batch_host = nullptr;
+    size_t batch_host_len = 0;
+    int batch_chunk_max = (getenv("QGD_BATCH_CHUNK") && atoi(getenv("QGD_BATCH_CHUNK")) >= 1) ? std::min(atoi(getenv("QGD_BATCH_CHUNK")), QGD_BATCH_CHUNK_MAX) : QGD_BATCH_CHUNK_MAX;
+    bool batch_path = false;
     std::vector<double> dense_w_host;
     bool have_basis = false, have_tables = false;
     StoredSweep sweep;

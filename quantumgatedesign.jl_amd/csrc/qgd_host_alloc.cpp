@@ -64,7 +64,7 @@ int pool_ensure(qgd_handle h, Pool &pool, const KeyedPlan &p, const char *fit, s
 }
 
 
-// the sensitivity pools (forced gradient, Hessian, Hessian-vector product, pullback, dense output) follow the grid and the control basis
+// the sensitivity pools (forced gradient, Hessian, Hessian-vector product, pullback, dense output, batch) follow the grid and the control basis
 void free_sensitivity_buffers(qgd_handle h)
 {
     for (int i = 0; i < N_SENS_POOLS; i++) pool_release(h->pools[i]);
@@ -575,6 +575,7 @@ void qgd_destroy(qgd_handle h)
     for (auto &p : h->phases) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     if (h->host_out) (void)hipHostFree(h->host_out);
     if (h->host_in) (void)hipHostFree(h->host_in);
+    if (h->batch_host) (void)hipHostFree(h->batch_host);
     if (h->mirror_host) (void)hipHostFree(h->mirror_host);
     if (h->mirror_ticket) (void)hipFree(h->mirror_ticket);
     if (h->k.stream && h->own_stream) (void)hipStreamDestroy(h->k.stream);

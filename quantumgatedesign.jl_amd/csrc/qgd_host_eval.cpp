@@ -446,6 +446,117 @@ static int forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, cons
 }
 
 
+// The device arrays of a batch chunk (POOL_BATCH) and its pinned staging buffer.  *members: in, the chunk the call would like;
+// out, the chunk it gets -- what the memory budget and the free device memory hold, never below one member.  A pool made for a
+// larger chunk of the same problem is kept as it is.
+static int batch_buffers(qgd_handle h, int n_pcof, int *members)
+{
+    const qgdk_ctx &k = h->k;
+    Pool &pool = h->pools[POOL_BATCH];
+    size_t st, sm, sc;
+    qgdk_tiny_batch_layout(&k, n_pcof, &st, &sm, &sc);
+    const size_t np = (size_t)n_pcof, per = st + 4 * sm + sc + QGD_TINY_BATCH_SMALL + np + (np + 5);      // doubles of one member
+    const std::vector<size_t> shape{(size_t)k.nt, (size_t)k.m, (size_t)k.n_ops, np};
+    size_t Kc = (size_t)*members;
+    if (pool.key.size() == 5 && std::equal(shape.begin(), shape.end(), pool.key.begin() + 1) && pool.key[0] >= Kc) Kc = pool.key[0];
+    else {
+        pool_release(pool);      // (what it held counts as free memory)
+        size_t limit = h->mem_budget, fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) == hipSuccess && (!limit || fr < limit)) limit = fr;
+        if (limit) Kc = std::max<size_t>(1, std::min(Kc, limit / (per * sizeof(double) + 9 * 64)));      // (9 buffers, dev_alloc pads each)
+    }
+    qgd_handle_s::BatchBufs &b = h->bt;
+    const int rc = pool_ensure(h, pool, {{Kc, shape[0], shape[1], shape[2], shape[3]}, {
+        {&b.pcofs, Kc * np}, {&b.tab, Kc * st}, {&b.Rg, Kc * sm}, {&b.Linv, Kc * sm}, {&b.psi, Kc * sm}, {&b.lam, Kc * sm},
+        {&b.cpart, Kc * sc}, {&b.small, Kc * QGD_TINY_BATCH_SMALL}, {&b.rows, Kc * (np + 5)}}},
+        "one member of a batch does not fit the memory budget or the free device memory", 0, [&]() -> int {
+            // (the status words: the front sets one, the batched k_contract_sum reads and clears it)
+            HIP_TRY(h, hipMemsetAsync(b.small, 0, Kc * QGD_TINY_BATCH_SMALL * sizeof(double), k.stream));
+            return QGD_OK;
+        });
+    if (rc) return rc;
+    const size_t stage = Kc * (2 * np + 5);
+    if (h->batch_host_len < stage) {
+        if (h->batch_host) (void)hipHostFree(h->batch_host);
+        h->batch_host = nullptr; h->batch_host_len = 0;
+        HIP_TRY(h, hipHostMalloc((void **)&h->batch_host, stage * sizeof(double), hipHostMallocDefault));
+        h->batch_host_len = stage;
+    }
+    *members = (int)std::min<size_t>(Kc, (size_t)*members);
+    return QGD_OK;
+}
+
+
+// Many coefficient vectors of one problem in one call.  On the small-problem path the members of a
+// chunk run side by side: one upload, four launches, one download, whatever the chunk holds.  Everywhere else the single
+// evaluations run one after another through the entry points above.
+int qgd_eval_batch(qgd_handle h, const double *pcofs, int32_t n_members, int32_t n_pcof, double *grads, double *out3,
+                   int32_t *member_status)
+{
+    if (!h) return QGD_ERR_ARGUMENT;
+    if (!pcofs || !out3) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    if (n_members < 1) return fail(h, QGD_ERR_ARGUMENT, "a batch needs at least one member");
+    if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_batch is single-GPU: this handle has a communicator or a partition");
+    HIP_TRY(h, hipSetDevice(h->device));
+    NEED_GRID(h);
+    qgdk_ctx &k = h->k;
+    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_eval_batch");
+    if (n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of a member's pcof does not match the control basis");
+    if (grads && !k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before a batch with gradients");
+    const size_t np = (size_t)n_pcof;
+    int first_singular = -1;
+    if (member_status) memset(member_status, 0, sizeof(int32_t) * (size_t)n_members);
+    if (!tiny_applies(h, pcofs, n_pcof)) {      // the loop route
+        for (int m = 0; m < n_members; m++) {
+            const double *p = pcofs + (size_t)m * np;
+            const int rc = grads ? qgd_discrete_adjoint(h, p, n_pcof, 0, grads + (size_t)m * np, nullptr, nullptr, nullptr, out3 + 3 * (size_t)m)
+                                 : qgd_eval_forward(h, p, n_pcof, nullptr, out3 + 3 * (size_t)m);
+            if (rc == QGD_ERR_NUMERIC) {
+                if (member_status) member_status[m] = 1;
+                if (first_singular < 0) first_singular = m;
+            } else if (rc) { sweep_void(h); h->batch_path = false; return rc; }
+        }
+        sweep_void(h);
+        h->batch_path = false;
+    } else {
+        int chunk = std::min((int)n_members, h->batch_chunk_max);
+        int rc = batch_buffers(h, n_pcof, &chunk);
+        if (rc) return rc;
+        sweep_void(h);
+        h->batch_path = true;
+        const qgd_handle_s::BatchBufs &b = h->bt;
+        const qgdk_tiny_batch dev{b.pcofs, b.tab, b.Rg, b.Linv, b.psi, b.lam, b.cpart, b.small, b.rows};
+        double *hin = h->batch_host, *hout = h->batch_host + (size_t)chunk * np;
+        for (int m0 = 0; m0 < n_members; m0 += chunk) {
+            const int Kc = std::min(chunk, (int)n_members - m0);
+            memcpy(hin, pcofs + (size_t)m0 * np, sizeof(double) * Kc * np);
+            HIP_TRY(h, hipMemcpyAsync(b.pcofs, hin, sizeof(double) * Kc * np, hipMemcpyHostToDevice, k.stream));
+            int e = qgdk_tiny_eval_batch(&k, &dev, Kc, n_pcof, grads ? 1 : 0);
+            if (!e) e = qgdk_contract_rows_batch(&k, &dev, Kc, n_pcof, grads ? k.nt : 0);
+            if (e) return fail(h, QGD_ERR_NO_DEVICE, std::string("batched small-problem evaluation failed to launch: ") + hipGetErrorString((hipError_t)e));
+            HIP_TRY(h, hipMemcpyAsync(hout, b.rows, sizeof(double) * Kc * (np + 5), hipMemcpyDeviceToHost, k.stream));
+            HIP_TRY(h, hipStreamSynchronize(k.stream));
+            for (int q = 0; q < Kc; q++) {
+                const double *row = hout + (size_t)q * (np + 5);
+                if (grads) memcpy(grads + (size_t)(m0 + q) * np, row, sizeof(double) * np);
+                memcpy(out3 + 3 * (size_t)(m0 + q), row + np, 3 * sizeof(double));
+                if (row[np + 3] != 0.0) {
+                    if (member_status) member_status[m0 + q] = 1;
+                    if (first_singular < 0) first_singular = m0 + q;
+                }
+            }
+        }
+    }
+    if (first_singular >= 0) {
+        const bool dirty = h->status_dirty;
+        const int rc = fail(h, QGD_ERR_NUMERIC, "singular implicit step matrix L(t_n) in member " + std::to_string(first_singular) + " of the batch");
+        if (h->batch_path) h->status_dirty = dirty;      // (the batched route has status words of its own, which it clears itself)
+        return rc;
+    }
+    return QGD_OK;
+}
+
+
 int qgd_eval_forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, const double *forcing,
                             double *uv_history, double *out3)
 {
@@ -681,12 +792,14 @@ int qgd_get_intermediate(qgd_handle h, const char *name, double *out, size_t cap
     else if (s == "selection") need = 4;
     else if (s == "small_path") need = 1;
     else if (s == "front_path") need = 1;
+    else if (s == "batch_path") need = 1;
     else return fail(h, QGD_ERR_ARGUMENT, "unknown intermediate '" + s + "'");
     if (needed) *needed = need;
     if (!out) return QGD_OK;
     if (capacity < need) return fail(h, QGD_ERR_ARGUMENT, "buffer too small");
     if (s == "small_path") { out[0] = h->sweep.kind == SWEEP_SMALL ? 1.0 : 0.0; return QGD_OK; }
     if (s == "front_path") { out[0] = h->sweep.front ? 1.0 : 0.0; return QGD_OK; }
+    if (s == "batch_path") { out[0] = h->batch_path ? 1.0 : 0.0; return QGD_OK; }
     if (s == "selection") {      // which kernel families this problem runs on (tests assert that a shape selects what it is meant to)
         out[0] = k.use_sparse ? 2.0 : (k.dense_gemm ? 1.0 : 0.0);      // 2 sparse (ELL), 1 N > 64 GEMM-style kernels, 0 dense N <= 64
         out[1] = (k.dense_gemm && !k.use_sparse) ? (double)qgdk_dense_sigma_form(&k) : -1.0;

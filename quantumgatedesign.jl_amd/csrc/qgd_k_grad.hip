@@ -443,14 +443,23 @@ __global__ __launch_bounds__(256) void k_contract(const double *__restrict__ G, 
 // (a rolled loop waited one memory round trip per row: 11 us for the 551 rows of the benchmark grid), then a fixed binary
 // tree over the 64 slots.  Same shape on every run => same bits.
 struct ResultMirror { double *host; unsigned long long seq; unsigned int *ticket; const double *scal; const int *status; };
+// BATCH (qgd_eval_batch, grid (coefficient tiles, members)): member b = blockIdx.y adds ITS rows, cpart + b * cpart_stride, into
+// row b of out[members][n_pcof + 5] = (grad | the member's three scalars | singular flag | status word) and clears the member's
+// status word for the next batch (it is the last kernel to read it).  The sums are those of the single launch: same bits.
+struct ContractBatch { long long cpart_stride; double *out; const double *scal; int *status; int scal_stride, status_stride; };
 
+template <bool BATCH>
 __global__ __launch_bounds__(1024) void k_contract_sum(const double *__restrict__ cpart, double *__restrict__ grad, int n_pcof, int rows,
                                                        int accumulate, const int *__restrict__ status, double *__restrict__ scal,
-                                                       const ResultMirror mir)
+                                                       const ResultMirror mir, const ContractBatch bt)
 {
     __shared__ double red[64][17];
+    if (BATCH) {
+        cpart += (size_t)blockIdx.y * bt.cpart_stride;
+        grad = bt.out + (size_t)blockIdx.y * (n_pcof + 5);
+    }
     // the singularity flag also travels as a double in the spare scalar slot, INSIDE the range the ranks all-reduce
-    if (status && blockIdx.x == 0 && threadIdx.x == 0 && *status) scal[3] = 1.0;
+    if (!BATCH && status && blockIdx.x == 0 && threadIdx.x == 0 && *status) scal[3] = 1.0;
     const int pl = threadIdx.x & 15, slot = threadIdx.x >> 4, p = blockIdx.x * 16 + pl;
     double tot = 0.0;
     if (p < n_pcof) {
@@ -473,6 +482,17 @@ __global__ __launch_bounds__(1024) void k_contract_sum(const double *__restrict_
         const double v = accumulate ? grad[p] + red[0][pl] : red[0][pl];
         grad[p] = v;
         if (mir.host) { mir.host[p] = v; __threadfence_system(); }      // (this thread's own posted write, ordered before the ticket below)
+    }
+    if (BATCH) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            const double *sc = bt.scal + (size_t)blockIdx.y * bt.scal_stride;
+            int *st = bt.status + (size_t)blockIdx.y * bt.status_stride;
+            const int flag = *st;
+            grad[n_pcof] = sc[0]; grad[n_pcof + 1] = sc[1]; grad[n_pcof + 2] = sc[2];
+            grad[n_pcof + 3] = flag ? 1.0 : 0.0; grad[n_pcof + 4] = (double)flag;
+            *st = 0;
+        }
+        return;
     }
     // Result mirror: the workgroup that draws the last ticket adds the scalars and the status word and then publishes the
     // sequence number the host polls (system-scope release: every workgroup's values are in host memory before it).
@@ -644,8 +664,20 @@ int qgdk_mirror_scalars(const qgdk_ctx *c)
 // rows of cpart added in a fixed order -> grad (and the host mirror): the tail of the small-problem path (qgd_k_tiny.hip)
 int qgdk_contract_rows(const qgdk_ctx *c, int rows)
 {
-    hipLaunchKernelGGL(k_contract_sum, dim3((c->n_pcof + 15) / 16), dim3(1024), 0, c->stream, c->cpart, c->grad, c->n_pcof, rows,
-                       0, c->status, c->scal, mirror_of(c));
+    hipLaunchKernelGGL(k_contract_sum<false>, dim3((c->n_pcof + 15) / 16), dim3(1024), 0, c->stream, c->cpart, c->grad, c->n_pcof, rows,
+                       0, c->status, c->scal, mirror_of(c), ContractBatch{});
+    return (int)hipGetLastError();
+}
+
+// the same for every member of a batch in one launch (rows = 0: a forward-only batch, only the scalars and the status travel)
+int qgdk_contract_rows_batch(const qgdk_ctx *c, const qgdk_tiny_batch *b, int members, int n_pcof, int rows)
+{
+    size_t st, sm, sc;
+    qgdk_tiny_batch_layout(c, n_pcof, &st, &sm, &sc);
+    ContractBatch bt{(long long)sc, b->rows, b->small, reinterpret_cast<int *>(b->small + 4), QGD_TINY_BATCH_SMALL, 2 * QGD_TINY_BATCH_SMALL};
+    ResultMirror none{};
+    hipLaunchKernelGGL(k_contract_sum<true>, dim3((n_pcof + 15) / 16, members), dim3(1024), 0, c->stream, b->cpart, (double *)nullptr, n_pcof, rows,
+                       0, (const int *)nullptr, (double *)nullptr, none, bt);
     return (int)hipGetLastError();
 }
 
@@ -655,8 +687,8 @@ int qgdk_gradient(const qgdk_ctx *c)
     if (c->use_sparse) {      // k_gradpoint_ell contracts with the basis itself: one row of cpart per (column group, time point)
         const int rc = qgdk_gradient_sparse(c);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_contract_sum, dim3((c->n_pcof + 15) / 16), dim3(1024), 0, c->stream, c->cpart, c->grad, c->n_pcof,
-                           (c->cp / 8) * c->nt, c->grad_accumulate, c->status, c->scal, mirror_of(c));
+        hipLaunchKernelGGL(k_contract_sum<false>, dim3((c->n_pcof + 15) / 16), dim3(1024), 0, c->stream, c->cpart, c->grad, c->n_pcof,
+                           (c->cp / 8) * c->nt, c->grad_accumulate, c->status, c->scal, mirror_of(c), ContractBatch{});
         return (int)hipGetLastError();
     }
     if (c->dense_gemm) {
@@ -694,8 +726,8 @@ int qgdk_contract(const qgdk_ctx *c)
                        c->dense_gemm ? qgdk_dense_sigma_planes(c) : c->cp / 8,      // one plane per contributing workgroup, added in order
                        c->cpart, c->n_pcof,
                        c->g_nt ? c->g_nt : c->nt, c->g_n0);
-    hipLaunchKernelGGL(k_contract_sum, dim3((c->n_pcof + 15) / 16), dim3(1024), 0, c->stream, c->cpart, c->grad, c->n_pcof, chunks,
-                       c->grad_accumulate, (const int *)nullptr, (double *)nullptr, mirror_of(c));
+    hipLaunchKernelGGL(k_contract_sum<false>, dim3((c->n_pcof + 15) / 16), dim3(1024), 0, c->stream, c->cpart, c->grad, c->n_pcof, chunks,
+                       c->grad_accumulate, (const int *)nullptr, (double *)nullptr, mirror_of(c), ContractBatch{});
     return (int)hipGetLastError();
 }
 

@@ -25,6 +25,11 @@
 // 107 us -- one compute unit can neither stream the control basis (300 KB) nor do the per-time-point work of 101 points
 // fast enough ("Round 4" (4)).  The general path's device buffers hold this path's compact arrays
 // afterwards, not its own intermediates: the host side marks the handle's stored history stale (qgd_host_eval.cpp: tiny_evaluate).
+//
+// A BATCH of evaluations (qgd_eval_batch) is the same four launches with a member axis: the kernels are
+// templates on whether there is one (front: on where the coefficients come from), member b = blockIdx.y (scan: blockIdx.x) reads
+// and writes its own share of every per-evaluation array, TinyArgs::ms_* apart.  The arithmetic is one text: a member's bits
+// are the single evaluation's.
 #include "qgd_kernels_common.h"
 #include <string.h>
 #include <algorithm>
@@ -249,7 +254,18 @@ __device__ __forceinline__ void matvecH(const double *__restrict__ Mx, const cx 
     }
 }
 
-template <int NMAX> struct TinyPcof { double v[NMAX]; };
+// where k_tiny_front takes its coefficients from: the kernel arguments (one evaluation: no upload), or row b of a
+// device array [members][n_pcof] (a batch, qgd_eval_batch: member b = blockIdx.y)
+template <int NMAX> struct TinyPcof {
+    double v[NMAX];
+    static constexpr bool batch = false;
+    __device__ __forceinline__ double at(int, int, int e) const { return v[e]; }
+};
+struct TinyPcofRows {
+    const double *rows;
+    static constexpr bool batch = true;
+    __device__ __forceinline__ double at(int b, int n_pcof, int e) const { return rows[(size_t)b * n_pcof + e]; }
+};
 
 struct TinyArgs {
     const double *ops;          // [(2+2 n_ops)][Np*Np] column-major planes (K_sys, S_sys, Asym_1, Sym_1, ...)
@@ -270,14 +286,23 @@ struct TinyArgs {
     int B, blen;                                // blocks of the scan
     double dt, tf;
     int o_small, o_P, o_psi, o_y, o_f, o_pib, o_bst, o_phi, o_red;     // LDS offsets of k_tiny_scan (doubles)
+    // a batch: member b's arrays lie b strides behind the pointers above (doubles; ms_status in ints)
+    long long ms_tab, ms_mat, ms_cpart;         // tab; each of Rg, Linv, psi, lam; cpart
+    int ms_scal, ms_status;
 };
+// member b's share of a per-member array (BATCH = false: the array itself, the stride is not read)
+template <bool BATCH, typename T>
+__device__ __forceinline__ T *tiny_member(T *p, const int b, const long long stride) { return BATCH ? p + (size_t)b * stride : p; }
 
 // ---------------------------------------------------------------------------
 // front: one workgroup (64 threads) per time point n
 // ---------------------------------------------------------------------------
-template <int M, int NO, int NMAX>
-__global__ __launch_bounds__(64) void k_tiny_front(const TinyArgs a, const TinyPcof<NMAX> pcof)
+template <int M, int NO, int NMAX, class PSRC>
+__global__ __launch_bounds__(64) void k_tiny_front(const TinyArgs a, const PSRC pcof)
 {
+    constexpr bool BATCH = PSRC::batch;
+    const int b = BATCH ? blockIdx.y : 0;               // (member arrays through tiny_member where they are used: pointers formed up
+                                                        //  here stay live across the kernel and cost the single call four SGPRs)
     __shared__ double PC[NMAX], OPS[(2 + 2 * NO) * 16], TABS[(M + 1) * NO * 2], CW[2 * (M + 1)], Y[32];
     __shared__ int NC[4], POFF[4];
     __shared__ long long GOFF[4];
@@ -286,7 +311,7 @@ __global__ __launch_bounds__(64) void k_tiny_front(const TinyArgs a, const TinyP
     const int TE = (M + 1) * n_ops * 2;
     const bool live = tid < 4;
     double *TAB = TABS - n * TE;                        // (the phase code below indexes TAB[n * TE + ...])
-    for (int e = tid; e < a.n_pcof; e += 64) PC[e] = pcof.v[e];
+    for (int e = tid; e < a.n_pcof; e += 64) PC[e] = pcof.at(b, a.n_pcof, e);
     for (int e = tid; e < (2 + 2 * n_ops) * 16; e += 64) {
         const int pl = e >> 4, r = (e >> 2) & 3, cc = e & 3;
         OPS[e] = (r < N && cc < N) ? a.ops[(size_t)pl * a.Np * a.Np + r + (size_t)a.Np * cc] : 0.0;
@@ -294,7 +319,7 @@ __global__ __launch_bounds__(64) void k_tiny_front(const TinyArgs a, const TinyP
     if (tid < 2 * (M + 1)) CW[tid] = a.cwv[tid];
     if (tid >= 32 && tid < 36) { const int k = tid - 32; NC[k] = a.nc[k]; POFF[k] = a.po[k]; GOFF[k] = a.go[k]; }
     if (n == 0) {
-        if (tid < 4) a.scal[tid] = 0.0;
+        if (tid < 4) tiny_member<BATCH>(a.scal, b, a.ms_scal)[tid] = 0.0;
     }
     // control tables of this time point: 16 lanes per entry (contiguous reads of the basis row), up to eight entries per
     // 16-lane group in flight, every load unconditional (clamped indices): one memory round trip
@@ -322,7 +347,7 @@ __global__ __launch_bounds__(64) void k_tiny_front(const TinyArgs a, const TinyP
                 #pragma unroll
                 for (int i = 0; i < 4; i++) { const int l = sub + 16 * i; sacc = __builtin_fma(gv[q][i], (l < ncq) ? PC[poq + l] : 0.0, sacc); }
                 sacc = row16_sum(sacc);
-                if (sub == 15 && eq < rows) { TABS[eq] = sacc; a.tab[(size_t)n * TE + eq] = sacc; }
+                if (sub == 15 && eq < rows) { TABS[eq] = sacc; tiny_member<BATCH>(a.tab, b, a.ms_tab)[(size_t)n * TE + eq] = sacc; }
             }
         }
     }
@@ -368,7 +393,7 @@ __global__ __launch_bounds__(64) void k_tiny_front(const TinyArgs a, const TinyP
                 }
             }
             st4(Y + j * 8, Lc);                         // L_n staged in LDS, R_n to global ([col][row][2])
-            st4(a.Rg + (size_t)n * 32 + j * 8, Rc);
+            st4(tiny_member<BATCH>(a.Rg, b, a.ms_mat) + (size_t)n * 32 + j * 8, Rc);
         }
     }
     __syncthreads();
@@ -393,7 +418,7 @@ __global__ __launch_bounds__(64) void k_tiny_front(const TinyArgs a, const TinyP
                 const double mg = Ar[r][p] * Ar[r][p] + Ai[r][p] * Ai[r][p];
                 if (mg > best) { best = mg; piv = r; }
             }
-            if (best == 0.0) { a.status[0] = 1; best = 1.0; }      // (an exactly singular pivot column; NaN coefficients propagate as on the general path and in the reference)
+            if (best == 0.0) { tiny_member<BATCH>(a.status, b, a.ms_status)[0] = 1; best = 1.0; }      // (an exactly singular pivot column; NaN coefficients propagate as on the general path and in the reference)
             #pragma unroll
             for (int r = p + 1; r < 4; r++) {
                 const bool sw = (r == piv);
@@ -432,15 +457,20 @@ __global__ __launch_bounds__(64) void k_tiny_front(const TinyArgs a, const TinyP
             Lij[r].re = (j == 0) ? Ir[r][0] : (j == 1) ? Ir[r][1] : (j == 2) ? Ir[r][2] : Ir[r][3];
             Lij[r].im = (j == 0) ? Ii[r][0] : (j == 1) ? Ii[r][1] : (j == 2) ? Ii[r][2] : Ii[r][3];
         }
-        st4(a.Linv + (size_t)n * 32 + j * 8, Lij);
+        st4(tiny_member<BATCH>(a.Linv, b, a.ms_mat) + (size_t)n * 32 + j * 8, Lij);
     }
 }
 
 // ---------------------------------------------------------------------------
 // scan: ONE workgroup, thread (n, j)
 // ---------------------------------------------------------------------------
+template <bool BATCH>
 __global__ __launch_bounds__(512) void k_tiny_scan(const TinyArgs a)
 {
+    const int b = BATCH ? blockIdx.x : 0;               // one workgroup per member
+    const double *const Rg_g = tiny_member<BATCH>(a.Rg, b, a.ms_mat), *const Linv_g = tiny_member<BATCH>(a.Linv, b, a.ms_mat);
+    double *const psi_g = tiny_member<BATCH>(a.psi, b, a.ms_mat), *const lam_g = tiny_member<BATCH>(a.lam, b, a.ms_mat);
+    double *const scal_g = tiny_member<BATCH>(a.scal, b, a.ms_scal);
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *SMALL = lds + a.o_small, *Pm = lds + a.o_P, *PSI = lds + a.o_psi, *Y = lds + a.o_y, *F = lds + a.o_f;
     double *PIB = lds + a.o_pib, *BST = lds + a.o_bst, *PHI = lds + a.o_phi, *RED = lds + a.o_red;
@@ -477,8 +507,8 @@ __global__ __launch_bounds__(512) void k_tiny_scan(const TinyArgs a)
     if (live && n >= 1) {
         double li[32];                                  // (L_n^-1)(r, cc) at [(cc * 4 + r) * 2]
         cx Rprev[4], Pcol[4];
-        ldm(a.Linv + (size_t)n * 32, li);
-        ld4(a.Rg + (size_t)(n - 1) * 32 + j * 8, Rprev);
+        ldm(Linv_g + (size_t)n * 32, li);
+        ld4(Rg_g + (size_t)(n - 1) * 32 + j * 8, Rprev);
         mv(li, Rprev, Pcol);
         #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -555,12 +585,12 @@ __global__ __launch_bounds__(512) void k_tiny_scan(const TinyArgs a)
         double gs = 0.0;
         for (int q = 0; q < (T >> 6); q++) gs += RED[q];
         gs *= a.dt / a.tf;
-        a.scal[0] = RED[32]; a.scal[1] = RED[33]; a.scal[2] = gs;
+        scal_g[0] = RED[32]; scal_g[1] = RED[33]; scal_g[2] = gs;
         RED[34] = gs;
     }
     __syncthreads();
     if (!a.gradient) {
-        if (tid == 0 && a.mirror) {
+        if (!BATCH && tid == 0 && a.mirror) {      // (a batch has no result mirror: its rows are downloaded)
             a.mirror[a.n_pcof] = RED[32]; a.mirror[a.n_pcof + 1] = RED[33]; a.mirror[a.n_pcof + 2] = RED[34]; a.mirror[a.n_pcof + 3] = 0.0;
             a.mirror[a.n_pcof + 4] = (double)__hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __threadfence_system();
@@ -636,8 +666,8 @@ __global__ __launch_bounds__(512) void k_tiny_scan(const TinyArgs a)
     if (live) {
         #pragma unroll
         for (int q = 0; q < 8; q++) {
-            a.psi[(size_t)n * 32 + j * 8 + q] = PSI[n * 32 + j * 8 + q];
-            a.lam[(size_t)n * 32 + j * 8 + q] = Y[n * 32 + j * 8 + q];
+            psi_g[(size_t)n * 32 + j * 8 + q] = PSI[n * 32 + j * 8 + q];
+            lam_g[(size_t)n * 32 + j * 8 + q] = Y[n * 32 + j * 8 + q];
         }
     }
 }
@@ -645,9 +675,13 @@ __global__ __launch_bounds__(512) void k_tiny_scan(const TinyArgs a)
 // ---------------------------------------------------------------------------
 // grad: one workgroup (64 threads) per time point n; threads 0..3 = state columns
 // ---------------------------------------------------------------------------
-template <int M, int NO>
+template <int M, int NO, bool BATCH>
 __global__ __launch_bounds__(64) void k_tiny_grad(const TinyArgs a)
 {
+    const int b = BATCH ? blockIdx.y : 0;
+    const double *const tab_g = tiny_member<BATCH>(a.tab, b, a.ms_tab), *const psi_g = tiny_member<BATCH>(a.psi, b, a.ms_mat);
+    const double *const lam_g = tiny_member<BATCH>(a.lam, b, a.ms_mat);
+    double *const cpart_g = tiny_member<BATCH>(a.cpart, b, a.ms_cpart);
     __shared__ double OPS[(2 + 2 * NO) * 16], TABS[(M + 1) * NO * 2], CW[2 * (M + 1)], SIGS[NO * M * 2], PSI[32], Y[64];
     __shared__ int NC[4], POFF[4];
     __shared__ long long GOFF[4];
@@ -660,11 +694,11 @@ __global__ __launch_bounds__(64) void k_tiny_grad(const TinyArgs a)
         const int pl = e >> 4, r = (e >> 2) & 3, cc = e & 3;
         OPS[e] = (r < N && cc < N) ? a.ops[(size_t)pl * a.Np * a.Np + r + (size_t)a.Np * cc] : 0.0;
     }
-    if (tid < TE) TABS[tid] = a.tab[(size_t)n * TE + tid];
+    if (tid < TE) TABS[tid] = tab_g[(size_t)n * TE + tid];
     if (tid < 2 * (M + 1)) CW[tid] = a.cwv[tid];
     if (tid >= 32 && tid < 36) { const int k = tid - 32; NC[k] = a.nc[k]; POFF[k] = a.po[k]; GOFF[k] = a.go[k]; }
-    if (tid < 32) PSI[tid] = a.psi[(size_t)n * 32 + tid];
-    Y[tid] = (tid < 32) ? a.lam[(size_t)n * 32 + tid] : ((n + 1 < nt) ? a.lam[(size_t)min(n + 1, nt - 1) * 32 + (tid - 32)] : 0.0);
+    if (tid < 32) PSI[tid] = psi_g[(size_t)n * 32 + tid];
+    Y[tid] = (tid < 32) ? lam_g[(size_t)n * 32 + tid] : ((n + 1 < nt) ? lam_g[(size_t)min(n + 1, nt - 1) * 32 + (tid - 32)] : 0.0);
     __syncthreads();
     double *PSIq = PSI - n * 32, *Yq = Y - n * 32;      // (the phase code indexes PSI[n * 32 + ...], Y[n * 32 + ...], Y[(n + 1) * 32 + ...])
     // ---- P8: gradient scalars of (time point n, column j)
@@ -779,7 +813,7 @@ __global__ __launch_bounds__(64) void k_tiny_grad(const TinyArgs a)
         double s = 0.0;
         #pragma unroll
         for (int d = 0; d < M; d++) { s = __builtin_fma(gvp[d], SIGS[(k * M + d) * 2], s); s = __builtin_fma(gvq[d], SIGS[(k * M + d) * 2 + 1], s); }
-        a.cpart[(size_t)n * a.n_pcof + p] = -s;
+        cpart_g[(size_t)n * a.n_pcof + p] = -s;
     }
 }
 
@@ -808,19 +842,46 @@ static void tiny_layout(const qgdk_ctx *c, TinyArgs &a, size_t &doubles, int &th
     doubles = (size_t)o;
 }
 
-template <int M, int NO>
-static int launch_tiny(const qgdk_ctx *c, TinyArgs &a, const TinyPcof<QGD_TINY_PCOF_MAX> &pc, size_t shm, int threads)
+// the launches of one evaluation, or of `members` of them side by side (PSRC::batch: a second grid dimension for the front and
+// the gradient kernel, one scan workgroup per member)
+template <int M, int NO, class PSRC>
+static int launch_tiny(const qgdk_ctx *c, TinyArgs &a, const PSRC &pc, size_t shm, int threads, int members)
 {
-    hipLaunchKernelGGL((k_tiny_front<M, NO, QGD_TINY_PCOF_MAX>), dim3(c->nt), dim3(64), 0, c->stream, a, pc);
-    SET_LDS_ONCE(k_tiny_scan, shm);
-    hipLaunchKernelGGL(k_tiny_scan, dim3(1), dim3(threads), shm, c->stream, a);
-    if (a.gradient) hipLaunchKernelGGL((k_tiny_grad<M, NO>), dim3(c->nt), dim3(64), 0, c->stream, a);
+    constexpr bool BATCH = PSRC::batch;
+    hipLaunchKernelGGL((k_tiny_front<M, NO, QGD_TINY_PCOF_MAX, PSRC>), dim3(c->nt, members), dim3(64), 0, c->stream, a, pc);
+    SET_LDS_ONCE(k_tiny_scan<BATCH>, shm);
+    hipLaunchKernelGGL(k_tiny_scan<BATCH>, dim3(members), dim3(threads), shm, c->stream, a);
+    if (a.gradient) hipLaunchKernelGGL((k_tiny_grad<M, NO, BATCH>), dim3(c->nt, members), dim3(64), 0, c->stream, a);
     return (int)hipGetLastError();
 }
-template <int M>
-static int launch_tiny_m(const qgdk_ctx *c, TinyArgs &a, const TinyPcof<QGD_TINY_PCOF_MAX> &pc, size_t shm, int threads)
+template <class PSRC>
+static int launch_tiny_any(const qgdk_ctx *c, TinyArgs &a, const PSRC &pc, size_t shm, int threads, int members)
 {
-    return c->n_ops <= 2 ? launch_tiny<M, 2>(c, a, pc, shm, threads) : launch_tiny<M, 4>(c, a, pc, shm, threads);
+#define TINY_M(M) return c->n_ops <= 2 ? launch_tiny<M, 2>(c, a, pc, shm, threads, members) : launch_tiny<M, 4>(c, a, pc, shm, threads, members)
+    switch (c->m) {
+    case 1: TINY_M(1);
+    case 2: TINY_M(2);
+    case 3: TINY_M(3);
+    case 4: TINY_M(4);
+    case 5: TINY_M(5);
+    default: TINY_M(6);
+    }
+#undef TINY_M
+}
+
+// what an evaluation's kernel arguments take from the context (the per-evaluation arrays and the member strides: the callers)
+static void tiny_args(const qgdk_ctx *c, TinyArgs &a, int n_pcof, int gradient)
+{
+    a.ops = c->ops; a.G = c->G; a.goff = c->goff; a.ncoef = c->ncoef; a.poff = c->poff;
+    a.psi0 = c->psi0; a.target = c->target; a.guard_diag = (c->have_guard == 2) ? c->guard_diag : nullptr;
+    for (int q = 0; q < 14; q++) a.cwv[q] = (q < 2 * (c->m + 1)) ? c->cw_host[q] : 0.0;
+    for (int q = 0; q < 4; q++) { a.nc[q] = (q < c->n_ops) ? c->ncoef_host[q] : 1; a.po[q] = (q < c->n_ops) ? c->poff_host[q] : 0; a.go[q] = (q < c->n_ops) ? c->goff_host[q] : 0; }
+    a.Np = c->Np; a.cp = c->cp; a.N = c->N; a.c = c->c; a.n_ops = c->n_ops; a.m = c->m; a.nt = c->nt; a.n_ess = c->n_ess; a.n_pcof = n_pcof;
+    a.cost = c->have_target ? 1 + c->cost_type : 0;
+    a.gradient = gradient;
+    a.dt = c->dt; a.tf = c->tf;
+    a.mirror = nullptr; a.mirror_seq = 0;
+    a.ms_tab = a.ms_mat = a.ms_cpart = 0; a.ms_scal = a.ms_status = 0;
 }
 
 extern "C" {
@@ -846,31 +907,41 @@ int qgdk_tiny_eval(const qgdk_ctx *c, const double *pcof_host, int n_pcof, int g
     TinyArgs a;
     size_t doubles; int threads;
     tiny_layout(c, a, doubles, threads);
-    a.ops = c->ops; a.G = c->G; a.goff = c->goff; a.ncoef = c->ncoef; a.poff = c->poff;
-    a.psi0 = c->psi0; a.target = c->target; a.guard_diag = (c->have_guard == 2) ? c->guard_diag : nullptr;
-    for (int q = 0; q < 14; q++) a.cwv[q] = (q < 2 * (c->m + 1)) ? c->cw_host[q] : 0.0;
-    for (int q = 0; q < 4; q++) { a.nc[q] = (q < c->n_ops) ? c->ncoef_host[q] : 1; a.po[q] = (q < c->n_ops) ? c->poff_host[q] : 0; a.go[q] = (q < c->n_ops) ? c->goff_host[q] : 0; }
+    tiny_args(c, a, n_pcof, gradient);
     // compact arrays in buffers the general path rewrites completely before it reads them (its hist[0] and lam[0] panels hold
     // the initial state and zeros from the allocation on: not those)
     a.tab = c->tab; a.Rg = c->R; a.Linv = c->LinvT; a.psi = c->L; a.lam = c->Pr; a.cpart = c->cpart;
     a.scal = c->scal; a.status = c->status;
     a.mirror = gradient ? nullptr : c->mirror_dev; a.mirror_seq = c->mirror_seq;
-    a.Np = c->Np; a.cp = c->cp; a.N = c->N; a.c = c->c; a.n_ops = c->n_ops; a.m = c->m; a.nt = c->nt; a.n_ess = c->n_ess; a.n_pcof = n_pcof;
-    a.cost = c->have_target ? 1 + c->cost_type : 0;
-    a.gradient = gradient;
-    a.dt = c->dt; a.tf = c->tf;
     TinyPcof<QGD_TINY_PCOF_MAX> pc;
     memset(&pc, 0, sizeof pc);
     memcpy(pc.v, pcof_host, sizeof(double) * n_pcof);
-    const size_t shm = doubles * sizeof(double);
-    switch (c->m) {
-    case 1: return launch_tiny_m<1>(c, a, pc, shm, threads);
-    case 2: return launch_tiny_m<2>(c, a, pc, shm, threads);
-    case 3: return launch_tiny_m<3>(c, a, pc, shm, threads);
-    case 4: return launch_tiny_m<4>(c, a, pc, shm, threads);
-    case 5: return launch_tiny_m<5>(c, a, pc, shm, threads);
-    default: return launch_tiny_m<6>(c, a, pc, shm, threads);
-    }
+    return launch_tiny_any(c, a, pc, doubles * sizeof(double), threads, 1);
+}
+
+// doubles one member of a batch keeps on the device: tab | Rg, Linv, psi, lam | cpart | scal(4), status (QGD_TINY_BATCH_SMALL)
+void qgdk_tiny_batch_layout(const qgdk_ctx *c, int n_pcof, size_t *tab, size_t *mat, size_t *cpart)
+{
+    *tab = (size_t)c->nt * (c->m + 1) * c->n_ops * 2; *mat = (size_t)c->nt * 32; *cpart = (size_t)c->nt * n_pcof;
+}
+
+// `members` evaluations with the coefficients b->pcofs[members][n_pcof] on the device, every per-member array of b one member
+// stride apart; the caller adds the cpart rows and gathers scal / status with qgdk_contract_rows_batch
+int qgdk_tiny_eval_batch(const qgdk_ctx *c, const qgdk_tiny_batch *b, int members, int n_pcof, int gradient)
+{
+    if (!qgdk_tiny_supported(c, n_pcof) || members < 1 || members > 65535) return (int)hipErrorInvalidValue;
+    TinyArgs a;
+    size_t doubles; int threads;
+    tiny_layout(c, a, doubles, threads);
+    tiny_args(c, a, n_pcof, gradient);
+    size_t st, sm, sc;
+    qgdk_tiny_batch_layout(c, n_pcof, &st, &sm, &sc);
+    a.tab = b->tab; a.Rg = b->Rg; a.Linv = b->Linv; a.psi = b->psi; a.lam = b->lam; a.cpart = b->cpart;
+    a.scal = b->small; a.status = reinterpret_cast<int *>(b->small + 4);
+    a.ms_tab = (long long)st; a.ms_mat = (long long)sm; a.ms_cpart = (long long)sc;
+    a.ms_scal = QGD_TINY_BATCH_SMALL; a.ms_status = 2 * QGD_TINY_BATCH_SMALL;
+    TinyPcofRows pc{b->pcofs};
+    return launch_tiny_any(c, a, pc, doubles * sizeof(double), threads, members);
 }
 
 } // extern "C"

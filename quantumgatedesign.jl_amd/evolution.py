@@ -15,6 +15,8 @@ behaviour as the reference:
                 observables)                                       gradient of a cost written in those three outputs
   eval_dense(prob, controls, pcof; order, refine, output, level_map, observables)   the same outputs between the grid points
                                                                    (Hermite dense output; hermite_interpolate is its statement)
+  discrete_adjoint_batch / eval_objective_batch(prob, controls, pcofs, target; order, cost_type)   many coefficient vectors in one
+                                                                   call (qgd_eval_batch); member k = the single call on pcofs[k]
 
 Julia's trailing ``!`` is spelled as a trailing underscore.  Arrays use the
 reference's column-major layouts (numpy ``order="F"``).
@@ -60,6 +62,52 @@ def real_to_complex(x):
     """state_vector_helpers.jl:78-87."""
     N = x.shape[0] // 2
     return x[:N] + 1j * x[N:]
+
+
+def batch_pcofs(pcofs, n_pcof):
+    """The coefficient vectors of a batch as the C ABI takes them: a C-contiguous float64 array ``[K, n_pcof]``.  Integer and
+    Fortran-ordered input is converted, a single vector is a batch of one; anything else raises ValueError."""
+    a = np.asarray(pcofs)
+    if np.iscomplexobj(a):
+        raise ValueError("pcofs must be real; got a complex array")
+    if a.ndim > 2:
+        raise ValueError(f"pcofs must be one vector or an array [K, n_pcof]; got {a.ndim} dimensions")
+    try:
+        a = np.ascontiguousarray(a, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"pcofs must be an array of real numbers: {e}") from None
+    if a.ndim < 2:
+        a = a.reshape(1, -1)
+    if a.shape[0] < 1:
+        raise ValueError("pcofs holds no member: a batch needs at least one coefficient vector")
+    if a.shape[1] != n_pcof:
+        raise ValueError(f"pcofs must have {n_pcof} coefficients per member; got {a.shape[1]}")
+    return a
+
+
+def finite_difference_points(pcof, dpcof):
+    """The ``2n`` points of the centred differences of eval_grad_finite_difference as one batch ``[2n, n]``: row ``i`` is
+    ``pcof + dpcof e_i``, row ``n + i`` is ``pcof - dpcof e_i`` (formed as ``pcof +- e`` with ``e = dpcof e_i``, the
+    expression of the loop this replaces: the same bits)."""
+    pcof = np.asarray(pcof, dtype=np.float64)
+    e = np.zeros((len(pcof), len(pcof)))
+    e[np.arange(len(pcof)), np.arange(len(pcof))] = dpcof
+    return np.ascontiguousarray(np.vstack([pcof + e, pcof - e]))
+
+
+def finite_difference_quotient(costs, dpcof):
+    """``(c_plus - c_minus) / (2 dpcof)`` of the costs at finite_difference_points, in that order."""
+    costs = np.asarray(costs, dtype=np.float64)
+    n = len(costs) // 2
+    return (costs[:n] - costs[n:]) / (2 * dpcof)
+
+
+def objective_from_scalars(scalars, N_ess, plain):
+    """The objective of every row of ``scalars [K, 3]`` (the three scalars of eval_forward): infidelity (``plain``) or the
+    tracking / norm cost, plus the guard penalty -- the expression of eval_grad_finite_difference's cost."""
+    sc = np.asarray(scalars, dtype=np.float64).reshape(-1, 3)
+    a, b, guard = sc[:, 0], sc[:, 1], sc[:, 2]      # (:Tracking / :Norm: a is the cost itself, b = 0)
+    return (1.0 - (a * a + b * b) / N_ess ** 2 if plain else a) + guard
 
 
 COST_TYPES = {"Infidelity": 0, ":Infidelity": 0, "Tracking": 1, ":Tracking": 1, "Norm": 2, ":Norm": 2}
@@ -458,6 +506,38 @@ class DeviceProblem:
             None if adjoint_forcing is None else _vp(adjoint_forcing), _vp(out3)))
         return grad, out3
 
+    def eval_batch(self, pcofs, gradient=True, out_grads=None, out_scalars=None):
+        """qgd_eval_batch: ``K`` coefficient vectors ``pcofs [K, n_pcof]`` in one call.  Member ``k`` gets bit for bit what
+        ``discrete_adjoint(pcofs[k])`` (``gradient=False``: ``eval_forward(pcofs[k])``) returns on this handle.  Returns
+        ``(grads [K, n_pcof] or None, scalars [K, 3], status [K] int32)``; ``status[k] = 1`` where a step matrix of member
+        ``k`` was singular -- that alone raises nothing here, the other members are valid.  Small problems (set_small_path) run
+        their members side by side, everything else one after another inside the library (batch_path_taken)."""
+        P = batch_pcofs(pcofs, self.n_pcof)
+        K = P.shape[0]
+        for a, shape, name in ((out_grads, (K, self.n_pcof), "out_grads"), (out_scalars, (K, 3), "out_scalars")):
+            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.shape != shape
+                                  or not a.flags.c_contiguous or not a.flags.writeable):
+                raise ValueError(f"{name} must be a writable C-contiguous float64 array of shape {shape}")
+        grads = (np.zeros((K, self.n_pcof)) if out_grads is None else out_grads) if gradient else None
+        scalars = np.zeros((K, 3)) if out_scalars is None else out_scalars
+        status = np.zeros(K, dtype=np.int32)
+        if getattr(self, "_general", None):               # non-linear controls: tables from the host at every member
+            for k in range(K):
+                if gradient:
+                    grads[k], scalars[k] = self.discrete_adjoint(P[k])
+                else:
+                    scalars[k] = self.eval_forward(P[k])
+            return grads, scalars, status
+        rc = self.lib.qgd_eval_batch(self.h, _vp(P), K, self.n_pcof, None if grads is None else _vp(grads), _vp(scalars),
+                                     _vp(status))
+        if rc != _lib.QGD_ERR_NUMERIC:
+            _lib.check(self.h, rc)
+        return grads, scalars, status
+
+    def batch_path_taken(self):
+        """Which route the last eval_batch call took: True the members side by side, False one after another."""
+        return bool(self.intermediate("batch_path")[0])
+
     def eval_adjoint(self, pcof, terminal_condition, forcing=None):
         if getattr(self, "_general", None):
             self._upload_general(pcof)
@@ -519,7 +599,7 @@ class DeviceProblem:
             return z[..., 0] + 1j * z[..., 1]
         if name == "repivoted":
             return int(out[0])
-        if name in ("selection", "small_path", "front_path"):
+        if name in ("selection", "small_path", "front_path", "batch_path"):
             return out
         if name == "sigma":
             return out.reshape(nt, self.n_ops, self.m, 2)
@@ -1061,19 +1141,51 @@ def eval_grad_finite_difference(prob, controls, pcof, target, dpcof=1e-5, order=
     dp.set_cost_type(cost_type)
     pcof = np.asarray(pcof, dtype=np.float64)
     plain = COST_TYPES[str(cost_type)] == 0
-
-    def cost(p):
-        a, b, guard = dp.eval_forward(p)       # (:Tracking / :Norm: a is the cost itself, b = 0)
-        return (1.0 - (a * a + b * b) / prob.N_ess_levels ** 2 if plain else a) + guard
-
-    grad = np.zeros(len(pcof))
     try:
-        for i in range(len(pcof)):
-            e = np.zeros(len(pcof)); e[i] = dpcof
-            grad[i] = (cost(pcof + e) - cost(pcof - e)) / (2 * dpcof)
+        # the 2 n_pcof points as one forward-only batch: one call instead of 2 n_pcof round trips
+        _, scalars, status = dp.eval_batch(finite_difference_points(pcof, dpcof), gradient=False)
+        _raise_singular(dp, status)
+        return finite_difference_quotient(objective_from_scalars(scalars, prob.N_ess_levels, plain), dpcof)
     finally:
         dp.set_cost_type("Infidelity")
-    return grad
+
+
+def _batch_problem(prob, controls, target, order, cost_type):
+    dp = device_problem(prob, order)
+    dp.set_controls(controls)
+    dp.set_target(target)
+    dp.set_cost_type(cost_type)
+    return dp
+
+
+def _raise_singular(dp, status):
+    if status.any():
+        raise _lib.QGDError(_lib.QGD_ERR_NUMERIC, f"singular implicit step matrix L(t_n) in members {np.flatnonzero(status).tolist()} of the batch")
+
+
+def discrete_adjoint_batch(prob, controls, pcofs, target, order=2, cost_type="Infidelity"):
+    """discrete_adjoint for ``K`` coefficient vectors ``pcofs [K, n_pcof]`` in one device call: the gradients ``[K, n_pcof]``,
+    row ``k`` bit for bit what ``discrete_adjoint(prob, controls, pcofs[k], target)`` returns (multi-start optimisation,
+    populations of an evolutionary optimiser, the points of a line search)."""
+    dp = _batch_problem(prob, controls, target, order, cost_type)
+    try:
+        grads, _, status = dp.eval_batch(pcofs, gradient=True)
+    finally:
+        dp.set_cost_type("Infidelity")
+    _raise_singular(dp, status)
+    return grads
+
+
+def eval_objective_batch(prob, controls, pcofs, target, order=2, cost_type="Infidelity"):
+    """The objective -- infidelity, or the tracking / norm cost, plus the guard penalty -- of ``K`` coefficient vectors
+    ``pcofs [K, n_pcof]`` in one device call: ``K`` values, formed from the scalars as eval_grad_finite_difference forms its costs."""
+    dp = _batch_problem(prob, controls, target, order, cost_type)
+    try:
+        _, scalars, status = dp.eval_batch(pcofs, gradient=False)
+    finally:
+        dp.set_cost_type("Infidelity")
+    _raise_singular(dp, status)
+    return objective_from_scalars(scalars, prob.N_ess_levels, COST_TYPES[str(cost_type)] == 0)
 
 
 def eval_adjoint(prob, controls, pcof, terminal_condition, order=2, forcing=None, lambda_derivatives=False):
