@@ -507,6 +507,27 @@ int qgd_eval_pullback(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t 
                       const double *expect_bar, const double *obs_re, const double *obs_im, int32_t n_obs,
                       double *grad);
 
+/* Pullback of the DENSE trajectory outputs to pcof: the same as qgd_eval_pullback for a cost written on the outputs of
+ * qgd_eval_dense, the Hermite interpolant of the sweep at `refine` points per step.  The cotangents have the shapes of the three
+ * qgd_eval_dense outputs, [2N | N or n_groups | n_obs, 1 + nsteps * refine, n_cols] (column-major), slot k at time k dt / refine;
+ * slot 0 is ignored and qgd_set_save_every has no part in it.  grad[n_pcof] = sum over the parts given of
+ * <bar, d output / d pcof>: the interpolation is transposed onto the state and the order/2 stage derivatives of every grid
+ * point, the reverse sweep of the stage-derivative recursion turns those into a cotangent of the grid states (which goes the
+ * way of qgd_eval_pullback: one adjoint sweep, one gradient contraction) and into the part through the control tables at the
+ * time points themselves, which is contracted with the basis and ADDED to the first -- in that order on every call.
+ * refine = 1 is qgd_eval_pullback with every grid point a slot: the same bits.  Sweep handling, buffers of its own, what it
+ * leaves of the stored evaluation and of the setup of qgd_eval_hessian_vec: as qgd_eval_pullback.  Deterministic.
+ * Refusals, before anything is launched: those of qgd_eval_pullback with the same codes; QGD_ERR_ARGUMENT for refine < 1 or
+ * 1 + nsteps * refine beyond a 32-bit integer; QGD_ERR_UNSUPPORTED for refine > 1 with order > 16; QGD_ERR_MEMORY when the
+ * buffers (1 + nsteps * refine panels of cotangents, (nsteps + 1)(order/2 + 1) of their transpose, three panel histories and the
+ * uploads, beside the interpolated panels of qgd_eval_dense) do not fit the memory budget or the free device memory.
+ * DESIGN.md section 4j. */
+int qgd_eval_dense_pullback(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed, int32_t refine,
+                            const double *states_bar,
+                            const double *pop_bar, const double *level_map, int32_t n_groups,
+                            const double *expect_bar, const double *obs_re, const double *obs_im, int32_t n_obs,
+                            double *grad);
+
 /* Operator path of the step-matrix and gradient kernels.  mode 0: automatic (sparse when every
  * row of the assembled Hamiltonian has at most min(16, N/2) entries and N <= 64 -- the drift +
  * a_k +/- a_k^dagger operators of src/multi_qudit_systems.jl -- else dense), 1: dense fp64 MFMA

@@ -372,6 +372,54 @@ function hip_eval_pullback(prob::SchrodingerProb, controls, pcof::Vector{Float64
     return grad
 end
 
+"Gradient with respect to pcof of a cost written on the outputs of hip_eval_dense (qgd_eval_dense_pullback): sum of
+<bar, d output / d pcof> over the cotangents given, each in the shape of its dense output at `refine` points per step:
+states_bar [2N, 1+nsteps*refine, c]; populations_bar [N or n_groups, ..]; expectations_bar [n_obs, ..] with `observables` as
+for hip_eval_expectations.  Slot 1 (the initial state) is ignored; independent of saveEveryNsteps; refine = 1 is
+hip_eval_pullback of every grid point.  One forward and one adjoint sweep on the device; no target is needed."
+function hip_eval_dense_pullback(prob::SchrodingerProb, controls, pcof::Vector{Float64}; order::Int=2, refine::Int=2,
+                                 states_bar::Union{Nothing,Array{Float64,3}}=nothing,
+                                 populations_bar::Union{Nothing,Array{Float64,3}}=nothing,
+                                 level_map::Union{Nothing,Matrix{Float64}}=nothing,
+                                 expectations_bar::Union{Nothing,Array{Float64,3}}=nothing, observables=nothing,
+                                 history_precomputed::Bool=false)
+    refine >= 1 || throw(ArgumentError("refine must be an integer >= 1"))
+    N, c, slots = prob.N_tot_levels, prob.N_initial_conditions, 1 + prob.nsteps * refine
+    states_bar === nothing && populations_bar === nothing && expectations_bar === nothing && throw(ArgumentError("no cotangent"))
+    states_bar === nothing || size(states_bar) == (2N, slots, c) || throw(DimensionMismatch("states_bar must be [$(2N), $slots, $c]"))
+    level_map === nothing || (populations_bar !== nothing && size(level_map, 2) == N) || throw(DimensionMismatch("level_map must be [n_groups, $N] and come with populations_bar"))
+    rows = level_map === nothing ? N : size(level_map, 1)
+    populations_bar === nothing || size(populations_bar) == (rows, slots, c) || throw(DimensionMismatch("populations_bar must be [$rows, $slots, $c]"))
+    (expectations_bar === nothing) == (observables === nothing) || throw(ArgumentError("expectations_bar and observables go together"))
+    n_obs, has_im = 0, false
+    obs_re, obs_im = zeros(0, 0, 0), zeros(0, 0, 0)
+    if observables !== nothing
+        obs = observables isa AbstractMatrix ? [observables] : collect(observables)
+        n_obs = length(obs)
+        n_obs >= 1 || throw(ArgumentError("no observable"))
+        size(expectations_bar) == (n_obs, slots, c) || throw(DimensionMismatch("expectations_bar must be [$n_obs, $slots, $c]"))
+        obs_re, obs_im = zeros(N, N, n_obs), zeros(N, N, n_obs)
+        for (j, o) in enumerate(obs)
+            size(o) == (N, N) || throw(DimensionMismatch("observable $j must be [$N, $N]"))
+            O = Matrix{ComplexF64}(o)
+            maximum(abs, O - O') <= 1e-12 * max(1.0, maximum(abs, O)) || throw(ArgumentError("observable $j is not Hermitian"))
+            obs_re[:, :, j] = real(O); obs_im[:, :, j] = imag(O)
+        end
+        has_im = any(!iszero, obs_im)
+    end
+    dp = device_problem(prob, order)
+    pc_ptr, pc_len = set_controls!(dp, prob, controls, pcof)
+    grad = zeros(length(pcof))
+    opt(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve pcof states_bar populations_bar level_map expectations_bar obs_re obs_im check(dp.handle, ccall((:qgd_eval_dense_pullback, libqgd), Cint,
+          (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64},
+           Ptr{Float64}, Int32, Ptr{Float64}),
+          dp.handle, pc_ptr, pc_len, history_precomputed ? 1 : 0, refine, opt(states_bar), opt(populations_bar), opt(level_map),
+          level_map === nothing ? 0 : rows, opt(expectations_bar), n_obs > 0 ? pointer(obs_re) : Ptr{Float64}(C_NULL),
+          has_im ? pointer(obs_im) : Ptr{Float64}(C_NULL), n_obs, grad))
+    return grad
+end
+
 "(infidelity, guard penalty) of the last evaluation of (prob, order) -- with :Tracking / :Norm: (cost, guard penalty)."
 function last_objective(prob::SchrodingerProb, order::Integer)
     dp = device_problem(prob, order)

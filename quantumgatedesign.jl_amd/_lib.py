@@ -30,6 +30,7 @@ EXPORTS = [
     "qgd_comm_unique_id", "qgd_comm_init_rccl", "qgd_comm_destroy", "qgd_comm_info", "qgd_set_save_every",
     "qgd_set_memory_budget", "qgd_get_memory_plan", "qgd_set_comm_timeout", "qgd_set_small_path",
     "qgd_eval_states", "qgd_eval_populations", "qgd_eval_expectations", "qgd_eval_pullback", "qgd_eval_dense", "qgd_eval_batch",
+    "qgd_eval_dense_pullback",
 ]
 QGD_CREATE_DEFER_GRID = 1
 
@@ -137,6 +138,8 @@ def lib():
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.qgd_eval_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.qgd_eval_dense_pullback.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.qgd_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L

@@ -265,6 +265,14 @@ int qgdk_expectations(const qgdk_ctx *c, const double *panels, long long src_n, 
    rows and columns zeros.  w_dev [refine-1][m+1][2]: the weights of the left and right end with dt^j folded in */
 int qgdk_interp(const qgdk_ctx *c, const double *hist, const double *dpsi, double *out, int refine, const double *w_dev,
                 hipStream_t stream);
+/* qgd_k_dense_pullback.hip (qgd_eval_dense_pullback).  qgdk_interp_transpose: the transpose of qgdk_interp -- G [1 + (nt-1) refine]
+   panels (cotangents of the dense panels) -> gbar [nt][m+1][Np][2cp] (cotangents of the state and the m stage derivatives of every
+   time point), w_dev the weight table of qgdk_interp; every panel of gbar is written.  qgdk_dense_pullback_sweep: the reverse sweep
+   of the stage-derivative recursion of c's history seeded by gbar -> F [nt] panels (the cotangent of the states, zero at n = 0)
+   and sigma [cp/8][nt][n_ops][m][2] (the part through the tables, in the layout qgdk_contract reads).  Neither changes sign:
+   with G = -dJ/dd (qgdk_pullback_forcing) F is the forcing of qgdk_hvp_adjoint and qgdk_contract's minus gives the plus. */
+int qgdk_interp_transpose(const qgdk_ctx *c, const double *G, double *gbar, int refine, const double *w_dev);
+int qgdk_dense_pullback_sweep(const qgdk_ctx *c, const double *gbar, double *F, double *sigma);
 #ifdef __cplusplus
 }
 #endif

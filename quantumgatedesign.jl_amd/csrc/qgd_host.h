@@ -2,7 +2,7 @@
 // launch macros, the phase timer and the internal entry points of each unit.
 //   qgd_host_alloc.cpp    handles: creation, validation (SchrodingerProb.jl:73-154), the time grid and its windows, setters
 //   qgd_host_eval.cpp     one evaluation: forward / adjoint phases, result transport, the evaluation entry points
-//   qgd_host_sens.cpp     sensitivities of the state to the parameters: the forced gradient, the exact Hessian, Hessian-vector products, pullbacks
+//   qgd_host_sens.cpp     sensitivities of the state to the parameters: the forced gradient, the exact Hessian, Hessian-vector products, pullbacks (grid points and dense output)
 //   qgd_host_output.cpp   reference-layout output arrays of a resident or windowed grid: the copy stream, staging, the one transport
 //   qgd_host_windows.cpp  time grids in bounded memory: window entry, the windowed forward and adjoint passes
 //   qgd_host_comm.cpp     several GPUs: the RCCL binding, the collective evaluation and its failure mode
@@ -91,7 +91,7 @@ struct Pool {
 };
 struct KeyedPlan { std::vector<size_t> key; std::vector<Buf> plan; };
 inline size_t pool_missing(const Pool &pool, const KeyedPlan &p) { return pool.key == p.key ? 0 : plan_bytes(p.plan); }
-enum { POOL_FORCED, POOL_HESS, POOL_HVP, POOL_PULLBACK, POOL_DENSE, POOL_BATCH, N_SENS_POOLS, POOL_FORCING = N_SENS_POOLS, POOL_STAGE, N_POOLS };
+enum { POOL_FORCED, POOL_HESS, POOL_HVP, POOL_PULLBACK, POOL_DENSE, POOL_BATCH, POOL_DENSE_PULLBACK, N_SENS_POOLS, POOL_FORCING = N_SENS_POOLS, POOL_STAGE, N_POOLS };
 
 struct qgd_handle_s {
     qgdk_ctx k{};
@@ -111,6 +111,7 @@ struct qgd_handle_s {
     //   POOL_PULLBACK  qgd_eval_pullback (pb); key (nt, n_pcof, the lengths of the five uploads)
     //   POOL_DENSE     qgd_eval_dense (dense_panels, dense_w); key (time points, refine, panel size, m, bits of dt)
     //   POOL_BATCH     qgd_eval_batch on the small-problem path (bt): the arrays of a chunk's members; key (chunk members, nt, m, n_ops, n_pcof)
+    //   POOL_DENSE_PULLBACK  qgd_eval_dense_pullback (dpb); key (time points, refine, n_pcof, m, bits of dt, the lengths of the five uploads)
     //   POOL_FORCING   qgd_eval_forward with a user forcing (k.ff_*, fsc_forcing); key (nt, scan blocks)
     //   POOL_STAGE     the staging buffers of the reference-layout outputs: no key, each made or grown on first need
     Pool pools[N_POOLS];
@@ -138,6 +139,14 @@ struct qgd_handle_s {
     // qgd_eval_dense: the interpolated panels [1 + (points-1) refine][Np][2cp] of a resident grid or of the
     // longest window, and the weight table of qgd_k_interp.hip with its host copy (the upload reads it)
     double *dense_panels = nullptr, *dense_w = nullptr;
+    // qgd_eval_dense_pullback: the cotangents of the dense panels (G) and of the state and stage
+    // derivatives of every time point (gbar), the forcing, y and mu of its adjoint sweep, sigma / cpart / gradient / scalars of
+    // its own and the caller's cotangents, level map and observable planes on the device -- nothing shared with the pullback
+    // or the Hessian-vector setup above; the dense panels and the weight table are POOL_DENSE's, under that pool's key
+    struct DensePullbackBufs {
+        double *G = nullptr, *gbar = nullptr, *F = nullptr, *Y = nullptr, *mu = nullptr, *sigma = nullptr, *cpart = nullptr, *gB = nullptr, *scal = nullptr;
+        double *sbar = nullptr, *pbar = nullptr, *map = nullptr, *ebar = nullptr, *planes = nullptr;
+    } dpb;
     // qgd_eval_batch: per member of a chunk the small-problem path's compact arrays, its scalars and
     // status word, its coefficients and its result row; the pinned staging buffer [pcofs | rows] of one chunk; the largest chunk
     // (QGD_BATCH_CHUNK, read when the handle is created: the tests force small chunks with it); the route of the last batch

@@ -465,6 +465,25 @@ class DeviceProblem:
                                                       0 if re is None else re.shape[2], _vp(grad)))
         return grad
 
+    def eval_dense_pullback(self, refine, pcof=None, states_bar=None, populations_bar=None, level_map=None,
+                            expectations_bar=None, observables=None, history_precomputed=False):
+        """Pullback of the DENSE outputs to pcof: eval_pullback for a cost written on eval_dense_states,
+        eval_dense_populations (same ``level_map``) and eval_dense_expectations (same ``observables``) at ``refine`` points per
+        step -- the cotangents have those results' shapes, ``[.., 1 + nsteps * refine, n_cols]``.  ``grad[n_pcof]``, exact for
+        the interpolant: the part that reaches pcof through the control tables at the grid points' own stage derivatives is
+        included.  Independent of set_save_every; slot 0 is ignored; ``refine = 1`` is eval_pullback of every grid point.
+        ``history_precomputed``: reuse the stored forward sweep when it belongs to this pcof.  No target is needed."""
+        refine = check_refine(refine)
+        sb, pb, lm, eb, re, im = pullback_cotangents(self.N, 1 + self.nsteps * refine, self.c, states_bar, populations_bar,
+                                                     level_map, expectations_bar, observables)
+        pc, ptr, n = self._pcof_arg(pcof)
+        grad = np.zeros(self.n_pcof)
+        opt = lambda a: None if a is None else _vp(a)
+        _lib.check(self.h, self.lib.qgd_eval_dense_pullback(self.h, ptr, n, 1 if history_precomputed else 0, refine, opt(sb),
+                                                            opt(pb), opt(lm), 0 if lm is None else lm.shape[0], opt(eb), opt(re),
+                                                            opt(im), 0 if re is None else re.shape[2], _vp(grad)))
+        return grad
+
     def discrete_adjoint(self, pcof, history_precomputed=False, uv_history=None, lambda_history=None,
                          adjoint_forcing=None):
         if getattr(self, "_general", None):
@@ -1056,6 +1075,21 @@ def eval_pullback(prob, controls, pcof, order=2, saveEveryNsteps=1, states_bar=N
         return dp.eval_pullback(pcof, states_bar, populations_bar, level_map, expectations_bar, observables)
     finally:
         dp.set_save_every(1)
+
+
+def eval_dense_pullback(prob, controls, pcof, order=2, refine=2, states_bar=None, populations_bar=None, level_map=None,
+                        expectations_bar=None, observables=None):
+    """Gradient with respect to pcof of a cost written on the outputs of eval_dense (states, populations with ``level_map``,
+    expectations of ``observables``) at ``refine`` points per step: ``sum <bar, d output / d pcof>`` over the cotangents given,
+    each in the shape of its output, ``[.., 1 + nsteps * refine, N_initial_conditions]`` (DeviceProblem.eval_dense_pullback,
+    DESIGN.md section 4j).  One forward and one adjoint sweep on the device, whatever the number of parameters or ``refine``.
+    Not in the reference."""
+    refine = check_refine(refine)
+    pullback_cotangents(prob.N_tot_levels, 1 + prob.nsteps * refine, prob.N_initial_conditions, states_bar, populations_bar,
+                        level_map, expectations_bar, observables)      # (refusals before a handle is made or anything is uploaded)
+    dp = device_problem(prob, order)
+    dp.set_controls(controls)
+    return dp.eval_dense_pullback(refine, pcof, states_bar, populations_bar, level_map, expectations_bar, observables)
 
 
 def eval_grad_forced(prob, controls, pcof, target, order=2, cost_type="Infidelity"):
