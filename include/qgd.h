@@ -434,6 +434,10 @@ int qgd_comm_info(qgd_handle h, int32_t *out3);
  * ends the job or calls qgd_comm_init_rccl again with a fresh id on every rank.  Argument and call-order errors are
  * raised before anything is launched, and a singular step matrix is summed into the reductions: those fail on every
  * rank alike, with their own codes, and leave the communicator intact.
+ * A librccl without ncclCommAbort leaves the library nothing to abort with: the communicator is leaked with its collective
+ * still on the handle's stream, and from then on every call that touches the device (everything but the setters and
+ * getters of host-side options, qgd_comm_info, qgd_last_error and qgd_destroy) returns QGD_ERR_COMM at once instead of
+ * waiting for that stream.  A fresh communicator is no recovery there: destroy the handle or end the process.
  * (The tests inject a local failure in front of each exchange with a hook that is NOT part of this library:
  * tests/hooks/qgd_test_hooks.cpp.) */
 int qgd_set_comm_timeout(qgd_handle h, double milliseconds);

@@ -7,6 +7,8 @@
 //   qgd_host_windows.cpp  time grids in bounded memory: window entry, the windowed forward and adjoint passes
 //   qgd_host_comm.cpp     several GPUs: the RCCL binding, the collective evaluation and its failure mode
 // There is no CPU fallback: without a GPU every compute entry point fails.
+// Every entry point that touches the device begins with ENTER (below), which also refuses a handle whose stream is dead; the
+// entry points that only read or write fields of the handle do not, and keep working on such a handle.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>      // types only: the library is bound at run time (dlopen), see RcclApi
@@ -226,7 +228,8 @@ struct qgd_handle_s {
     // the other ranks then run into their own bound instead of waiting for this one forever.
     double comm_timeout_ms = 30000.0;
     bool stream_dead = false;           // a communicator had to be leaked with a collective stuck on the stream (no ncclCommAbort in this librccl):
-                                        // every later compute entry point fails fast with QGD_ERR_COMM, qgd_destroy does not wait for the stream
+                                        // every later entry point that touches the device is refused with QGD_ERR_COMM by enter(), before any HIP call that
+                                        // could wait for the stream (setters and getters of host fields keep working); qgd_destroy does not wait for it either
     int comm_fail_at = 0;               // != 0: pretend a local failure in front of collective #n (set only by the tests' fault injector, tests/hooks/qgd_test_hooks.cpp -- no entry point of the library writes it)
     bool grid_ready = false;            // QGD_CREATE_DEFER_GRID: the time grid is allocated by the first entry point that needs it
     bool comm_pending = false;          // qgd_comm_init_rccl is re-allocating the grid for the communicator it is about to
@@ -367,9 +370,20 @@ inline bool sweep_reusable(qgd_handle h, const double *pcof, int n_pcof)
 }
 
 
-// (QGD_CREATE_DEFER_GRID) entry points that read or size anything by the time grid allocate it first
-#define NEED_GRID(h)                                                                           \
-    do { if (!(h)->grid_ready) { int rg__ = alloc_grid(h); if (rg__) return rg__; } } while (0)
+// How every entry point of the C ABI that touches the device begins, behind the refusals it makes from its arguments alone:
+// a null handle is QGD_ERR_ARGUMENT; the handle's device becomes the thread's (QGD_ERR_NO_DEVICE); a handle whose stream is dead
+// (qgd_handle_s::stream_dead) is refused with QGD_ERR_COMM before any HIP call that could wait for that stream; a captured
+// graph is dropped unless ENTER_KEEPS_GRAPH; the time grid of a QGD_CREATE_DEFER_GRID handle is allocated unless ENTER_NO_GRID
+// (entry points that neither read nor size anything by the grid, or that allocate it anew themselves).
+enum { ENTER_KEEPS_GRAPH = 1, ENTER_NO_GRID = 2 };
+int enter(qgd_handle h, unsigned flags = 0);
+#define ENTER(h, ...) do { int re__ = qgdh::enter((h), ##__VA_ARGS__); if (re__) return re__; } while (0)
+
+// history_precomputed with nothing stored that it could refer to: the refusal (else QGD_OK)
+inline int refuse_reuse(qgd_handle h, int history_precomputed)
+{
+    return history_precomputed && h->sweep.kind == SWEEP_NONE ? fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation") : QGD_OK;
+}
 
 
 #define K_TRY(h, expr)                                                                         \

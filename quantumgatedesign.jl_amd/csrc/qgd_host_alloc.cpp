@@ -303,6 +303,18 @@ int alloc_grid(qgd_handle h)
     return QGD_OK;
 }
 
+
+// the prologue of the entry points (qgd_host.h: ENTER); a handle that passes pays two branches beside its hipSetDevice
+int enter(qgd_handle h, unsigned flags)
+{
+    if (!h) return fail(h, QGD_ERR_ARGUMENT, "null handle");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->stream_dead) return fail(h, QGD_ERR_COMM, "a communicator of this handle was leaked with a collective stuck on its stream: the handle accepts no further evaluation");
+    if (!(flags & ENTER_KEEPS_GRAPH)) drop_graph(h);      // (behind the dead-stream check: dropping a graph is a HIP call)
+    if (!(flags & ENTER_NO_GRID) && !h->grid_ready) return alloc_grid(h);      // (QGD_CREATE_DEFER_GRID: the first entry point that reads or sizes anything by the grid)
+    return QGD_OK;
+}
+
 }  // namespace qgdh
 
 using namespace qgdh;
@@ -585,10 +597,8 @@ void qgd_destroy(qgd_handle h)
 
 int qgd_set_nsteps(qgd_handle h, int32_t nsteps, double tf)
 {
-    if (h) drop_graph(h);
-    if (!h) return QGD_ERR_ARGUMENT;
     if (nsteps < 1 || !(tf > 0)) return fail(h, QGD_ERR_ARGUMENT, "nsteps and tf must be positive");
-    HIP_TRY(h, hipSetDevice(h->device));
+    ENTER(h, ENTER_NO_GRID);
     h->nsteps = nsteps; h->k.tf = tf;
     return alloc_grid(h);
 }
@@ -596,9 +606,8 @@ int qgd_set_nsteps(qgd_handle h, int32_t nsteps, double tf)
 
 int qgd_set_target(qgd_handle h, const double *target_real)
 {
-    if (h) drop_graph(h);
-    if (!h || !target_real) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
+    if (!target_real) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h, ENTER_NO_GRID);
     qgdk_ctx &k = h->k;
     const size_t PWc = 2 * k.cp;
     std::vector<double> t((size_t)k.Np * PWc, 0.0);
@@ -626,10 +635,8 @@ int qgd_set_cost_type(qgd_handle h, int32_t cost_type)
 
 int qgd_set_control_basis(qgd_handle h, const int32_t *n_coeff, const double *const *Gp, const double *const *Gq)
 {
-    if (h) drop_graph(h);
-    if (!h || (h->k.n_ops && (!n_coeff || !Gp || !Gq))) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    if (h && h->k.n_ops && (!n_coeff || !Gp || !Gq)) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h);
     qgdk_ctx &k = h->k;
     free_pool(h->basis_bufs);
     free_sensitivity_buffers(h);
@@ -711,10 +718,8 @@ int qgd_set_control_basis(qgd_handle h, const int32_t *n_coeff, const double *co
 
 int qgd_set_control_tables(qgd_handle h, const double *pt, const double *qt)
 {
-    if (h) drop_graph(h);
-    if (!h || !pt || !qt) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    if (!pt || !qt) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h);
     qgdk_ctx &k = h->k;
     if (h->chunks_eff > 1) {      // a windowed grid: the tables of the whole grid stay on the host, each window uploads its slice
         const size_t all = (size_t)k.nt_glob * (k.m + 1) * k.n_ops;
@@ -746,10 +751,8 @@ int qgd_set_control_tables(qgd_handle h, const double *pt, const double *qt)
 // ---------------------------------------------------------------------------
 int qgd_set_partition(qgd_handle h, int32_t rank, int32_t world)
 {
-    if (h) drop_graph(h);
-    if (!h) return QGD_ERR_ARGUMENT;
     if (world < 1 || rank < 0 || rank >= world) return fail(h, QGD_ERR_ARGUMENT, "rank/world out of range");
-    HIP_TRY(h, hipSetDevice(h->device));
+    ENTER(h, ENTER_NO_GRID);
     h->part_rank = rank; h->part_world = world;
     return alloc_grid(h);
 }
@@ -757,8 +760,8 @@ int qgd_set_partition(qgd_handle h, int32_t rank, int32_t world)
 
 int qgd_get_partition(qgd_handle h, int32_t *out8)
 {
-    if (!h || !out8) return QGD_ERR_ARGUMENT;
-    NEED_GRID(h);
+    if (!out8) return QGD_ERR_ARGUMENT;
+    ENTER(h, ENTER_KEEPS_GRAPH);
     const qgdk_ctx &k = h->k;
     out8[0] = k.n_off; out8[1] = k.n_off + k.nt - 1;   // first / last global time point of the window
     // One GPU working through the grid in windows (qgd_set_memory_budget): the windows are the library's business -- the
@@ -773,9 +776,7 @@ int qgd_get_partition(qgd_handle h, int32_t *out8)
 
 int qgd_set_stream(qgd_handle h, void *stream)
 {
-    if (h) drop_graph(h);
-    if (!h) return QGD_ERR_ARGUMENT;
-    HIP_TRY(h, hipSetDevice(h->device));
+    ENTER(h, ENTER_NO_GRID);
     HIP_TRY(h, hipStreamSynchronize(h->k.stream));
     if (h->own_stream && h->k.stream) (void)hipStreamDestroy(h->k.stream);
     h->k.stream = (hipStream_t)stream;
@@ -786,8 +787,8 @@ int qgd_set_stream(qgd_handle h, void *stream)
 
 int qgd_register_host_buffer(qgd_handle h, void *ptr, size_t bytes)
 {
-    if (!h || !ptr || !bytes) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
+    if (!ptr || !bytes) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h, ENTER_KEEPS_GRAPH | ENTER_NO_GRID);
     if (find_reg(h, ptr, bytes)) return QGD_OK;
     hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterMapped);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, QGD_ERR_NO_DEVICE, std::string("hipHostRegister: ") + hipGetErrorString(e)); }
@@ -800,8 +801,8 @@ int qgd_register_host_buffer(qgd_handle h, void *ptr, size_t bytes)
 
 int qgd_unregister_host_buffer(qgd_handle h, void *ptr)
 {
-    if (!h || !ptr) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
+    if (!ptr) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h, ENTER_KEEPS_GRAPH | ENTER_NO_GRID);
     for (size_t i = 0; i < h->regs.size(); i++)
         if (h->regs[i].host == ptr) {
             if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
@@ -815,8 +816,8 @@ int qgd_unregister_host_buffer(qgd_handle h, void *ptr)
 
 int qgd_set_operator_path(qgd_handle h, int32_t mode)
 {
-    if (h) drop_graph(h);
     if (!h) return QGD_ERR_ARGUMENT;
+    drop_graph(h);
     if (mode < 0 || mode > 2) return fail(h, QGD_ERR_ARGUMENT, "operator path: 0 automatic, 1 dense, 2 sparse");
     if (mode == 2 && !h->sparse_available)
         return fail(h, QGD_ERR_UNSUPPORTED, "the operators are too dense (or N > 64) for the sparse kernels");
@@ -854,10 +855,8 @@ int qgd_set_lambda_derivatives(qgd_handle h, int32_t on)
 
 int qgd_set_memory_budget(qgd_handle h, size_t bytes)
 {
-    if (h) drop_graph(h);
-    if (!h) return QGD_ERR_ARGUMENT;
-    if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_STATE, "a partitioned handle keeps its window resident: set the budget before the partition");
-    HIP_TRY(h, hipSetDevice(h->device));
+    if (h && (h->comm || h->part_world != 1)) return fail(h, QGD_ERR_STATE, "a partitioned handle keeps its window resident: set the budget before the partition");
+    ENTER(h, ENTER_NO_GRID);
     h->mem_budget = bytes;
     return alloc_grid(h);          // (invalidates control basis and histories, like qgd_set_nsteps)
 }
@@ -865,8 +864,8 @@ int qgd_set_memory_budget(qgd_handle h, size_t bytes)
 
 int qgd_get_memory_plan(qgd_handle h, int64_t *out4)
 {
-    if (!h || !out4) return QGD_ERR_ARGUMENT;
-    NEED_GRID(h);
+    if (!out4) return QGD_ERR_ARGUMENT;
+    ENTER(h, ENTER_KEEPS_GRAPH);
     const qgdk_ctx &k = h->k;
     out4[0] = h->chunks_eff; out4[1] = (int64_t)k.bpr * k.scan_blen; out4[2] = (int64_t)h->window_bytes; out4[3] = (int64_t)h->mem_budget;
     return QGD_OK;
@@ -896,8 +895,8 @@ int qgd_set_timing(qgd_handle h, int32_t mode, const char *phase)
 
 int qgd_get_timings(qgd_handle h, const char **names, float *ms, int32_t cap, int32_t *n)
 {
-    if (!h || !n) return QGD_ERR_ARGUMENT;
-    (void)hipSetDevice(h->device);
+    if (!n) return QGD_ERR_ARGUMENT;
+    ENTER(h, ENTER_KEEPS_GRAPH | ENTER_NO_GRID);
     (void)hipStreamSynchronize(h->k.stream);
     int cnt = 0;
     for (size_t i = 0; i < h->phases.size(); i++) {

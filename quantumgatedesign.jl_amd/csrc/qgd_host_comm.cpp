@@ -181,7 +181,7 @@ int comm_discrete_adjoint(qgd_handle h, const double *pcof, int n_pcof, int hist
     // what every rank gets alike is refused before anything is launched (no collective is left half-entered)
     if (pcof && n_pcof != h->k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
     if (!pcof && !h->have_tables && h->k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
-    if (history_precomputed && h->sweep.kind == SWEEP_NONE) return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+    if (int rc = refuse_reuse(h, history_precomputed)) return rc;
     return comm_local_error(h, comm_discrete_adjoint_body(h, pcof, n_pcof, history_precomputed, grad, uv_history, lambda_history, adjoint_forcing, out3));
 }
 
@@ -294,13 +294,12 @@ int qgd_comm_destroy(qgd_handle h)
 
 int qgd_comm_init_rccl(qgd_handle h, const void *unique_id, int32_t rank, int32_t world, int32_t shard)
 {
-    if (h) drop_graph(h);
-    if (!h || !unique_id) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    if (!unique_id) return fail(h, QGD_ERR_ARGUMENT, "null argument");
     if (world < 1 || rank < 0 || rank >= world) return fail(h, QGD_ERR_ARGUMENT, "rank/world out of range");
     if (shard != QGD_SHARD_TIME && shard != QGD_SHARD_COLUMNS) return fail(h, QGD_ERR_ARGUMENT, "shard: 0 time windows, 1 column blocks");
+    ENTER(h, ENTER_NO_GRID);      // (in front of the binding: a handle whose stream is dead gets that answer with or without a librccl)
     RcclApi &R = rccl();
     if (!R.ok) return fail(h, QGD_ERR_COMM, R.err);
-    HIP_TRY(h, hipSetDevice(h->device));
     int rc = qgd_comm_destroy(h);
     if (rc) return rc;
     // time windows: the rank's window of the grid (invalidates control basis and histories, like qgd_set_nsteps);

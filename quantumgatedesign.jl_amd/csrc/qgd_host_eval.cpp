@@ -40,7 +40,6 @@ static bool front_applies(qgd_handle h, const double *pcof, int n_pcof)
 int forward_begin(qgd_handle h, const double *pcof, int n_pcof, bool allow_front)
 {
     qgdk_ctx &k = h->k;
-    if (h->stream_dead) return fail(h, QGD_ERR_COMM, "a communicator of this handle was leaked with a collective stuck on its stream: the handle accepts no further evaluation");
     if (pcof && !h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before passing pcof");
     if (pcof && n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
     if (!pcof && !h->have_tables && k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
@@ -266,9 +265,7 @@ extern "C" {
 
 int qgd_eval_forward(qgd_handle h, const double *pcof, int32_t n_pcof, double *uv_history, double *out3)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    ENTER(h, ENTER_KEEPS_GRAPH);
     qgdk_ctx &k = h->k;
     if (h->comm) return comm_eval_forward(h, pcof, n_pcof, uv_history, out3);
     if (h->chunks_eff > 1 && uv_history) {      // the history of a chunked grid comes out window by window
@@ -292,9 +289,8 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, int32
                          double *grad, double *uv_history, double *lambda_history, double *adjoint_forcing,
                          double *out3)
 {
-    if (!h || !grad) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    if (!grad) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h, ENTER_KEEPS_GRAPH);
     qgdk_ctx &k = h->k;
     if (!k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before qgd_discrete_adjoint");
     if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_discrete_adjoint");
@@ -302,14 +298,14 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, int32
     if (h->part_world != 1) return fail(h, QGD_ERR_STATE, "partitioned handle: use the qgd_dist_* entry points, or give the handle a communicator (qgd_comm_init_rccl)");
     int rc;
     if (h->chunks_eff > 1) {      // bounded-memory time grid: forward pass over the windows, adjoint pass back over them
-        if (history_precomputed && h->sweep.kind == SWEEP_NONE) return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+        if ((rc = refuse_reuse(h, history_precomputed))) return rc;
         // (uv_history is an output: a reused forward pass would have nothing to copy it from, so the pass is redone)
         if ((uv_history || !(history_precomputed && sweep_reusable(h, pcof, n_pcof))) && (rc = chunked_forward(h, pcof, n_pcof, uv_history))) return rc;
         if ((rc = chunked_adjoint(h, lambda_history, adjoint_forcing))) return rc;
         return fetch_results(h, grad, out3);
     }
     if (!uv_history && !lambda_history && !adjoint_forcing && tiny_applies(h, pcof, n_pcof)) {
-        if (history_precomputed && h->sweep.kind == SWEEP_NONE) return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+        if ((rc = refuse_reuse(h, history_precomputed))) return rc;
         return tiny_evaluate(h, pcof, n_pcof, true, grad, out3);      // (four launches redo the sweep faster than the stored one could be reused)
     }
     // full evaluation, nothing but [grad | scalars] coming back, no event bracketing: replay the captured launch sequence
@@ -355,8 +351,7 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, int32
     // history_precomputed: the reference differentiates the history it is GIVEN with the pcof it is given
     // (eval_grad_discrete_adjoint.jl:118-124).  The device keeps its own copy of the last forward sweep; it is
     // reused only when it was computed from this very pcof, otherwise the sweep is simply redone.
-    if (history_precomputed && h->sweep.kind == SWEEP_NONE)
-        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+    if ((rc = refuse_reuse(h, history_precomputed))) return rc;
     const bool reuse = history_precomputed && sweep_reusable(h, pcof, n_pcof);
     if (reuse) {
         // the terminal right-hand side may not have been written if the target was set later
@@ -395,13 +390,10 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, int32
 // windows, the overlaps come from the final state; uv_history (stage derivatives w_j = D_j w_0 + E_j included) window by
 // window as in chunked_forward.
 // (states: qgd_eval_states with a forcing -- the forced states alone, no stage derivatives)
+// Both callers have entered and dropped a captured graph.
 static int forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, const double *forcing,
                           double *uv_history, double *states, double *out3)
 {
-    if (h) drop_graph(h);
-    if (!h || !forcing) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
     qgdk_ctx &k = h->k;
     if (h->part_world != 1) return fail(h, QGD_ERR_STATE, "partitioned handle: the forced forward sweep is single-GPU");
     const int W = h->chunks_eff;
@@ -493,12 +485,10 @@ static int batch_buffers(qgd_handle h, int n_pcof, int *members)
 int qgd_eval_batch(qgd_handle h, const double *pcofs, int32_t n_members, int32_t n_pcof, double *grads, double *out3,
                    int32_t *member_status)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
     if (!pcofs || !out3) return fail(h, QGD_ERR_ARGUMENT, "null argument");
     if (n_members < 1) return fail(h, QGD_ERR_ARGUMENT, "a batch needs at least one member");
-    if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_batch is single-GPU: this handle has a communicator or a partition");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    if (h && (h->comm || h->part_world != 1)) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_batch is single-GPU: this handle has a communicator or a partition");
+    ENTER(h, ENTER_KEEPS_GRAPH);
     qgdk_ctx &k = h->k;
     if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_eval_batch");
     if (n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of a member's pcof does not match the control basis");
@@ -560,19 +550,20 @@ int qgd_eval_batch(qgd_handle h, const double *pcofs, int32_t n_members, int32_t
 int qgd_eval_forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, const double *forcing,
                             double *uv_history, double *out3)
 {
+    if (!forcing) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h);
     return forward_forced(h, pcof, n_pcof, forcing, uv_history, nullptr, out3);
 }
 
 
 // The forward sweep (or, history_precomputed under the rule of qgd_discrete_adjoint, the stored one) and nothing of it but what
-// `obs` names.  The sweep record ends as qgd_eval_forward without an output array leaves it.
+// `obs` names.  The sweep record ends as qgd_eval_forward without an output array leaves it.  (refuse_reuse: every caller has
+// asked already, before its uploads.)
 static int observe_eval(qgd_handle h, const double *pcof, int n_pcof, int history_precomputed, const Observe &obs, double *out3)
 {
     qgdk_ctx &k = h->k;
     int rc;
     const int save = obs.refine ? 1 : h->save_every;      // (the dense output returns every sub-point)
-    if (history_precomputed && h->sweep.kind == SWEEP_NONE)
-        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
     if (h->chunks_eff > 1) {      // one window is resident at a time: the pass over the windows is redone, each hands out its share
         if ((rc = chunked_forward(h, pcof, n_pcof, nullptr, save, &obs))) return rc;
         return fetch_results(h, nullptr, out3);
@@ -590,12 +581,10 @@ static int observe_eval(qgd_handle h, const double *pcof, int n_pcof, int histor
 
 int qgd_eval_states(qgd_handle h, const double *pcof, int32_t n_pcof, const double *forcing, double *states, double *out3)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
     if (!states) return fail(h, QGD_ERR_ARGUMENT, "null output array");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    ENTER(h, ENTER_KEEPS_GRAPH);
     if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_states is single-GPU: this handle has a communicator or a partition");
-    if (forcing) return forward_forced(h, pcof, n_pcof, forcing, nullptr, states, out3);
+    if (forcing) { drop_graph(h); return forward_forced(h, pcof, n_pcof, forcing, nullptr, states, out3); }
     return observe_eval(h, pcof, n_pcof, 0, Observe{OBS_STATES, 0, states}, out3);
 }
 
@@ -603,18 +592,15 @@ int qgd_eval_states(qgd_handle h, const double *pcof, int32_t n_pcof, const doub
 int qgd_eval_populations(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
                          const double *level_map, int32_t n_groups, double *populations, double *out3)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
     if (!populations) return fail(h, QGD_ERR_ARGUMENT, "null output array");
     if (level_map && n_groups < 1) return fail(h, QGD_ERR_ARGUMENT, "a level map needs n_groups >= 1");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    ENTER(h, ENTER_KEEPS_GRAPH);
     if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_populations is single-GPU: this handle has a communicator or a partition");
-    if (history_precomputed && h->sweep.kind == SWEEP_NONE)
-        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+    int rc;
+    if ((rc = refuse_reuse(h, history_precomputed))) return rc;
     if (level_map) {
         const size_t len = (size_t)n_groups * h->k.N;
-        int rc = grow_stage(h, h->obs_map, len);
-        if (rc) return rc;
+        if ((rc = grow_stage(h, h->obs_map, len))) return rc;
         HIP_TRY(h, hipMemcpyAsync(h->obs_map.p, level_map, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
     }
     return observe_eval(h, pcof, n_pcof, history_precomputed, Observe{OBS_POPULATIONS, level_map ? n_groups : 0, populations}, out3);
@@ -624,17 +610,14 @@ int qgd_eval_populations(qgd_handle h, const double *pcof, int32_t n_pcof, int32
 int qgd_eval_expectations(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
                           const double *obs_re, const double *obs_im, int32_t n_obs, double *expect, double *out3)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
     if (!expect) return fail(h, QGD_ERR_ARGUMENT, "null output array");
     if (!obs_re || n_obs < 1) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_expectations needs obs_re and n_obs >= 1");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    ENTER(h, ENTER_KEEPS_GRAPH);
     if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_expectations is single-GPU: this handle has a communicator or a partition");
-    if (history_precomputed && h->sweep.kind == SWEEP_NONE)
-        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
+    int rc;
+    if ((rc = refuse_reuse(h, history_precomputed))) return rc;
     const size_t len = (size_t)n_obs * h->k.N * h->k.N;
-    int rc = grow_stage(h, h->obs_planes, (obs_im ? 2 : 1) * len);
-    if (rc) return rc;
+    if ((rc = grow_stage(h, h->obs_planes, (obs_im ? 2 : 1) * len))) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->obs_planes.p, obs_re, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
     if (obs_im) HIP_TRY(h, hipMemcpyAsync(h->obs_planes.p + len, obs_im, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
     return observe_eval(h, pcof, n_pcof, history_precomputed, Observe{OBS_EXPECTATIONS, 0, expect, n_obs, obs_im != nullptr}, out3);
@@ -648,24 +631,21 @@ int qgd_eval_dense(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t his
                    const double *level_map, int32_t n_groups, const double *obs_re, const double *obs_im, int32_t n_obs,
                    double *out, double *out3)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
     if (!out) return fail(h, QGD_ERR_ARGUMENT, "null output array");
-    if (refine < 1 || (long long)h->nsteps * refine + 1 > 0x7fffffffLL)
+    if (refine < 1 || (h && (long long)h->nsteps * refine + 1 > 0x7fffffffLL))
         return fail(h, QGD_ERR_ARGUMENT, "refine must be >= 1 and 1 + nsteps * refine fit a 32-bit integer");
     if (kind != QGD_DENSE_STATES && kind != QGD_DENSE_POPULATIONS && kind != QGD_DENSE_EXPECTATIONS)
         return fail(h, QGD_ERR_ARGUMENT, "unknown kind of dense output");
     if (kind == QGD_DENSE_POPULATIONS && level_map && n_groups < 1) return fail(h, QGD_ERR_ARGUMENT, "a level map needs n_groups >= 1");
     if (kind == QGD_DENSE_EXPECTATIONS && (!obs_re || n_obs < 1)) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_dense needs obs_re and n_obs >= 1 for expectation values");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    ENTER(h, ENTER_KEEPS_GRAPH);
     const qgdk_ctx &k = h->k;
     if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_dense is single-GPU: this handle has a communicator or a partition");
     if (pcof && !h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before passing pcof");
     if (pcof && n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
     if (!pcof && !h->have_tables && k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
-    if (history_precomputed && h->sweep.kind == SWEEP_NONE)
-        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
     int rc;
+    if ((rc = refuse_reuse(h, history_precomputed))) return rc;
     if (refine > 1 && (rc = dense_buffers(h, refine))) return rc;      // (QGD_ERR_MEMORY before the sweep is touched)
     Observe obs{OBS_STATES, 0, out, 0, false, refine};
     if (kind == QGD_DENSE_POPULATIONS) {
@@ -694,10 +674,8 @@ int qgd_eval_dense(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t his
 int qgd_eval_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, const double *terminal_condition,
                      const double *forcing, double *lambda_history)
 {
-    if (h) drop_graph(h);
-    if (!h || !terminal_condition || !lambda_history) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    if (!terminal_condition || !lambda_history) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h);
     qgdk_ctx &k = h->k;
     if (h->part_world != 1) return fail(h, QGD_ERR_STATE, "partitioned handle: eval_adjoint is single-GPU");
     const int W = h->chunks_eff;
@@ -751,10 +729,8 @@ int qgd_eval_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof, const dou
 int qgd_apply_hamiltonian(qgd_handle h, int32_t time_index, int32_t deriv_order, int32_t use_adjoint,
                           const double *in, double *out)
 {
-    if (h) drop_graph(h);
-    if (!h || !in || !out) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    if (!in || !out) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h);
     qgdk_ctx &k = h->k;
     NEEDS_RESIDENT_GRID(h, "qgd_apply_hamiltonian");
     if (time_index < 0 || time_index >= k.nt || deriv_order < 0 || deriv_order > k.m)
@@ -778,9 +754,8 @@ int qgd_apply_hamiltonian(qgd_handle h, int32_t time_index, int32_t deriv_order,
 
 int qgd_get_intermediate(qgd_handle h, const char *name, double *out, size_t capacity, size_t *needed)
 {
-    if (!h || !name) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    if (!name) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h, ENTER_KEEPS_GRAPH);
     qgdk_ctx &k = h->k;
     const size_t Np = k.Np, N = k.N, nt = k.nt, PW = 2 * Np, panel = Np * PW, pl = Np * Np;
     std::string s(name);
@@ -808,7 +783,6 @@ int qgd_get_intermediate(qgd_handle h, const char *name, double *out, size_t cap
         return QGD_OK;
     }
     NEEDS_RESIDENT_GRID(h, "qgd_get_intermediate");
-    if (h->stream_dead) return fail(h, QGD_ERR_COMM, "a communicator of this handle was leaked with a collective stuck on its stream");
     const bool matrices = s == "L" || s == "R" || s == "Linv" || s == "P";
     if ((h->sweep.kind == SWEEP_SMALL && s != "repivoted") || (h->sweep.front && h->sweep.has_pcof && matrices)) {
         // the small-problem path keeps no intermediates, the front's step matrices are the same-point form's (L^H, R^H, L^-H,
@@ -865,8 +839,8 @@ int qgd_get_intermediate(qgd_handle h, const char *name, double *out, size_t cap
 int qgd_exchange_buffer(qgd_handle h, int32_t which, void **dev_ptr, size_t *total_doubles, size_t *own_offset,
                         size_t *own_doubles)
 {
-    if (!h || !dev_ptr || !total_doubles || !own_offset || !own_doubles) return QGD_ERR_ARGUMENT;
-    NEED_GRID(h);
+    if (!dev_ptr || !total_doubles || !own_offset || !own_doubles) return QGD_ERR_ARGUMENT;
+    ENTER(h, ENTER_KEEPS_GRAPH);
     const qgdk_ctx &k = h->k;
     const size_t pl = (size_t)k.Np * k.Np, hstep = (size_t)k.Np * 2 * k.cp, W = (size_t)k.part_world;
     if (which == 0) {          // block propagators, all-gather
@@ -888,9 +862,7 @@ int qgd_exchange_buffer(qgd_handle h, int32_t which, void **dev_ptr, size_t *tot
 
 int qgd_dist_forward_begin(qgd_handle h, const double *pcof, int32_t n_pcof)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    ENTER(h, ENTER_KEEPS_GRAPH);
     if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called first");
     return forward_begin(h, pcof, n_pcof);
 }
@@ -898,8 +870,7 @@ int qgd_dist_forward_begin(qgd_handle h, const double *pcof, int32_t n_pcof)
 
 int qgd_dist_forward_end(qgd_handle h)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
-    HIP_TRY(h, hipSetDevice(h->device));
+    ENTER(h, ENTER_KEEPS_GRAPH | ENTER_NO_GRID);
     const int rc = forward_end(h);
     if (!rc) sweep_done(h, SWEEP_GENERAL, nullptr, 0);      // (no pcof: a partitioned handle never reuses its sweep, qgd_discrete_adjoint refuses it)
     return rc;
@@ -908,8 +879,7 @@ int qgd_dist_forward_end(qgd_handle h)
 
 int qgd_dist_adjoint_begin(qgd_handle h)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
-    HIP_TRY(h, hipSetDevice(h->device));
+    ENTER(h, ENTER_KEEPS_GRAPH | ENTER_NO_GRID);
     if (!h->k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called first");
     if (!sweep_stored(h)) return fail(h, QGD_ERR_STATE, "no forward evaluation to differentiate (qgd_dist_forward_* first)");
     return adjoint_begin(h);
@@ -918,16 +888,14 @@ int qgd_dist_adjoint_begin(qgd_handle h)
 
 int qgd_dist_adjoint_end(qgd_handle h)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
-    HIP_TRY(h, hipSetDevice(h->device));
+    ENTER(h, ENTER_KEEPS_GRAPH | ENTER_NO_GRID);
     return adjoint_end(h);
 }
 
 
 int qgd_dist_finish(qgd_handle h, double *grad, double *out3)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
-    HIP_TRY(h, hipSetDevice(h->device));
+    ENTER(h, ENTER_KEEPS_GRAPH | ENTER_NO_GRID);
     return fetch_results(h, grad, out3);
 }
 
@@ -942,9 +910,8 @@ int qgd_dist_finish(qgd_handle h, double *grad, double *out3)
 // ---------------------------------------------------------------------------
 int qgd_cols_forward(qgd_handle h, const double *pcof, int32_t n_pcof)
 {
-    if (!h || !pcof) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    if (!pcof) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h, ENTER_KEEPS_GRAPH);
     if (!h->k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called first");
     if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called first");
     return run_forward(h, pcof, n_pcof);        // scal = this rank's <w,R>, <w,T>, guard: exchange buffer 3
@@ -953,8 +920,7 @@ int qgd_cols_forward(qgd_handle h, const double *pcof, int32_t n_pcof)
 
 int qgd_cols_adjoint(qgd_handle h, int32_t keep_scalars)
 {
-    if (!h) return QGD_ERR_ARGUMENT;
-    HIP_TRY(h, hipSetDevice(h->device));
+    ENTER(h, ENTER_KEEPS_GRAPH | ENTER_NO_GRID);
     qgdk_ctx &k = h->k;
     if (!sweep_stored(h)) return fail(h, QGD_ERR_STATE, "no forward evaluation to differentiate (qgd_cols_forward first)");
     { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal_given(&k)); }      // y_N from the all-reduced overlaps

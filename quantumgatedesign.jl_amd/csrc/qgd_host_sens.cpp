@@ -32,11 +32,9 @@ static int forced_buffers(qgd_handle h, size_t nt, size_t B)
 static size_t forced_missing(qgd_handle h) { return pool_missing(h->pools[POOL_FORCED], forced_plan(h, (size_t)h->k.nt, (size_t)h->k.scan_blocks)); }
 
 
-// how both second-order entry points begin, and what they refuse (`name`: the entry point, `what`: its result, for the messages)
-static int second_order_enter(qgd_handle h, const double *pcof, int n_pcof, const std::string &name, const char *what)
+// what both second-order entry points refuse once they have entered (`name`: the entry point, `what`: its result, for the messages)
+static int second_order_refusals(qgd_handle h, const double *pcof, int n_pcof, const std::string &name, const char *what)
 {
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
     const qgdk_ctx &k = h->k;
     if (h->part_world != 1 || h->comm) return fail(h, QGD_ERR_STATE, std::string("partitioned handle: ") + what + " is single-GPU");
     if (!k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before " + name);
@@ -235,8 +233,9 @@ static qgdk_ctx adjoint_context(const qgdk_ctx &k, double *F, double *Y, double 
 }
 
 
-// The arguments of a pullback entry point (`name`: for the messages), what both entry points refuse before anything is launched,
-// their forward sweep, and the grid-point pullback itself with slot k at time point k * save.
+// The arguments of a pullback entry point (`name`: for the messages), what both entry points refuse before anything is launched
+// (from their arguments alone, in front of ENTER, and of the handle's state behind it), their forward sweep, and the grid-point
+// pullback itself with slot k at time point k * save.
 struct PullbackCall {
     const char *name;
     const double *pcof; int32_t n_pcof, history_precomputed;
@@ -245,16 +244,18 @@ struct PullbackCall {
     double *grad;
 };
 
-static int pullback_enter(qgd_handle h, const PullbackCall &p)
+static int pullback_arguments(qgd_handle h, const PullbackCall &p)
 {
-    const std::string name = p.name;
-    if (h) drop_graph(h);
-    if (!h || !p.grad) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    if (!p.states_bar && !p.pop_bar && !p.expect_bar) return fail(h, QGD_ERR_ARGUMENT, name + " needs at least one of states_bar, pop_bar, expect_bar");
+    if (!p.grad) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    if (!p.states_bar && !p.pop_bar && !p.expect_bar) return fail(h, QGD_ERR_ARGUMENT, std::string(p.name) + " needs at least one of states_bar, pop_bar, expect_bar");
     if (p.level_map && p.n_groups < 1) return fail(h, QGD_ERR_ARGUMENT, "a level map needs n_groups >= 1");
     if (p.expect_bar && (!p.obs_re || p.n_obs < 1)) return fail(h, QGD_ERR_ARGUMENT, "expect_bar needs obs_re and n_obs >= 1");
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    return QGD_OK;
+}
+
+static int pullback_refusals(qgd_handle h, const PullbackCall &p)
+{
+    const std::string name = p.name;
     const qgdk_ctx &k = h->k;
     if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before " + name);
     if (h->part_world != 1 || h->comm) return fail(h, QGD_ERR_STATE, "partitioned handle: the pullback is single-GPU");
@@ -263,9 +264,7 @@ static int pullback_enter(qgd_handle h, const PullbackCall &p)
     if (k.N > 64) return fail(h, QGD_ERR_UNSUPPORTED, name + " supports N <= 64");
     if (k.n_ops < 1) return fail(h, QGD_ERR_UNSUPPORTED, name + " needs control operators");
     if (!p.pcof && !h->have_tables) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
-    if (p.history_precomputed && h->sweep.kind == SWEEP_NONE)
-        return fail(h, QGD_ERR_STATE, "history_precomputed without a previous forward evaluation");
-    return QGD_OK;
+    return refuse_reuse(h, p.history_precomputed);
 }
 
 // the general two-point forward sweep unless history_precomputed finds one of the same pcof, and the stage derivatives
@@ -311,10 +310,8 @@ extern "C" {
 
 int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, double *grad)
 {
-    if (h) drop_graph(h);
-    if (!h || !grad) return fail(h, QGD_ERR_ARGUMENT, "null argument");     // (pcof may be NULL when the tables were set directly)
-    HIP_TRY(h, hipSetDevice(h->device));
-    NEED_GRID(h);
+    if (!grad) return fail(h, QGD_ERR_ARGUMENT, "null argument");     // (pcof may be NULL when the tables were set directly)
+    ENTER(h);
     qgdk_ctx &k = h->k;
     if (!k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before qgd_eval_grad_forced");
     if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_eval_grad_forced");
@@ -351,11 +348,11 @@ int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, doubl
 // of sensitivities kept, then the second-order contraction of qgd_k_hessian.hip.  The terminal part is host arithmetic on s_N.
 int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *hess, double *grad)
 {
-    if (h) drop_graph(h);
-    if (!h || !hess) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    if (!hess) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    ENTER(h);
     qgdk_ctx &k = h->k;
     int rc;
-    if ((rc = second_order_enter(h, pcof, n_pcof, "qgd_eval_hessian", "the Hessian"))) return rc;
+    if ((rc = second_order_refusals(h, pcof, n_pcof, "qgd_eval_hessian", "the Hessian"))) return rc;
     if ((rc = hess_buffers(h))) return rc;
     if ((rc = second_order_setup(h, pcof, n_pcof))) return rc;      // (lambda; the adjoint gradient is unused)
     const size_t nt = k.nt, np = (size_t)k.n_pcof, hstepS = (size_t)k.Np * 2 * np * k.cp;
@@ -399,12 +396,12 @@ int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *h
 // the adjoint sweep with that forcing (mu), the gradient kernels with mu in place of lambda, k_hvp_contract.
 int qgd_eval_hessian_vec(qgd_handle h, const double *pcof, int32_t n_pcof, const double *v, int32_t n_vec, double *hv, double *grad)
 {
-    if (h) drop_graph(h);
-    if (!h || !v || !hv) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    if (!v || !hv) return fail(h, QGD_ERR_ARGUMENT, "null argument");
     if (n_vec < 1) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_hessian_vec needs at least one vector");
+    ENTER(h);
     qgdk_ctx &k = h->k;
     int rc;
-    if ((rc = second_order_enter(h, pcof, n_pcof, "qgd_eval_hessian_vec", "the Hessian-vector product"))) return rc;
+    if ((rc = second_order_refusals(h, pcof, n_pcof, "qgd_eval_hessian_vec", "the Hessian-vector product"))) return rc;
     const size_t nt = k.nt, np = (size_t)k.n_pcof, hstep = (size_t)k.Np * 2 * k.cp;
     if ((rc = hvp_buffers(h))) return rc;
     auto &b = h->hv;
@@ -446,8 +443,11 @@ int qgd_eval_pullback(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t 
                       double *grad)
 {
     const PullbackCall p{"qgd_eval_pullback", pcof, n_pcof, history_precomputed, states_bar, pop_bar, level_map, n_groups, expect_bar, obs_re, obs_im, n_obs, grad};
-    const int rc = pullback_enter(h, p);
-    return rc ? rc : pullback_grid(h, p, h->save_every);
+    int rc;
+    if ((rc = pullback_arguments(h, p))) return rc;
+    ENTER(h);
+    if ((rc = pullback_refusals(h, p))) return rc;
+    return pullback_grid(h, p, h->save_every);
 }
 
 
@@ -464,12 +464,12 @@ int qgd_eval_dense_pullback(qgd_handle h, const double *pcof, int32_t n_pcof, in
                             double *grad)
 {
     const PullbackCall p{"qgd_eval_dense_pullback", pcof, n_pcof, history_precomputed, states_bar, pop_bar, level_map, n_groups, expect_bar, obs_re, obs_im, n_obs, grad};
-    if (h && grad && (refine < 1 || (long long)h->nsteps * refine + 1 > 0x7fffffffLL)) {
-        drop_graph(h);
+    if (grad && (refine < 1 || (h && (long long)h->nsteps * refine + 1 > 0x7fffffffLL)))
         return fail(h, QGD_ERR_ARGUMENT, "refine must be >= 1 and 1 + nsteps * refine fit a 32-bit integer");
-    }
     int rc;
-    if ((rc = pullback_enter(h, p))) return rc;
+    if ((rc = pullback_arguments(h, p))) return rc;
+    ENTER(h);
+    if ((rc = pullback_refusals(h, p))) return rc;
     if (refine == 1) return pullback_grid(h, p, 1);      // (whatever qgd_set_save_every says: the dense output returns every point)
     qgdk_ctx &k = h->k;
     if (k.m > 8) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_dense_pullback with refine > 1 supports order <= 16 (the interpolation kernels cover order/2 <= 8)");

@@ -18,6 +18,8 @@ def lib():
         _lib = C.CDLL(_SO)
         _lib.qgd_comm_debug_fail_at.argtypes = [C.c_void_p, C.c_int32]
         _lib.qgd_comm_debug_fail_at.restype = C.c_int
+        _lib.qgd_test_stream_dead.argtypes = [C.c_void_p, C.c_int32]
+        _lib.qgd_test_stream_dead.restype = C.c_int
     return _lib
 
 
@@ -26,3 +28,10 @@ def comm_debug_fail_at(dp, collective):
     rc = lib().qgd_comm_debug_fail_at(dp.h, int(collective))
     if rc:
         raise RuntimeError(f"qgd_comm_debug_fail_at: {rc}")
+
+
+def stream_dead(dp, on):
+    """Mark the stream of DeviceProblem `dp` dead (or alive again), as a leaked communicator leaves it; nothing is made to hang."""
+    rc = lib().qgd_test_stream_dead(dp.h, int(bool(on)))
+    if rc:
+        raise RuntimeError(f"qgd_test_stream_dead: {rc}")
