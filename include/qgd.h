@@ -251,11 +251,24 @@ int qgd_discrete_adjoint(qgd_handle h, const double *pcof, int32_t n_pcof,
  * infidelity against the target; :Tracking is 0.5 |w_N - target|^2 and :Norm is 0.5 |w_N|^2 over the stacked real
  * states of all columns (the reference marks both untested; here they are tested like :Infidelity -- adjoint against
  * forced and centred differences, and against the oracle).  With a cost type other than :Infidelity the scalars
- * out3 of qgd_eval_forward / qgd_discrete_adjoint are { cost, 0, guard penalty }.  Anything else: QGD_ERR_ARGUMENT
- * (the reference throws "Invalid cost type"). */
+ * out3 of qgd_eval_forward / qgd_discrete_adjoint are { cost, 0, guard penalty }.
+ * :StateTransfer (not in the reference) is the per-column fidelity: with o_j = t_j^H psi_j = a_j - i b_j the overlap of
+ * column j of the final state with column j of the target and c = n_cols,
+ *   J = 1 - (1/c) sum_j |o_j|^2,      y_N = (2/c)(a_j R_j + b_j T_j) + f_N  column by column,
+ * so every column may arrive with a phase of its own (several state transfers at once, a gate up to local Z phases).
+ * Target columns are expected to have unit norm; nothing normalises them.  It runs on every evaluation path -- small
+ * problems, the fused front, N > 64, windowed grids, a time partition, qgd_eval_batch, qgd_eval_grad_forced,
+ * qgd_eval_hessian, qgd_eval_hessian_vec -- with the per-column sums added in a fixed order (the same bits on every
+ * run).  Column shards are refused with it (a rank cannot know the global column count): qgd_cols_forward,
+ * qgd_cols_adjoint and the evaluations of a QGD_SHARD_COLUMNS communicator return QGD_ERR_UNSUPPORTED before anything
+ * is launched or sent.  qgd_get_intermediate "column_overlaps" reads (a_j, b_j) back.
+ * Setting the type is host-only; a change drops a captured launch sequence, the Hessian-vector setup and a stored
+ * front sweep, as before.  Anything else: QGD_ERR_ARGUMENT (the reference throws "Invalid cost type") and the handle's
+ * type stays as it was. */
 #define QGD_COST_INFIDELITY 0
 #define QGD_COST_TRACKING   1
 #define QGD_COST_NORM       2
+#define QGD_COST_STATE_TRANSFER 3
 int qgd_set_cost_type(qgd_handle h, int32_t cost_type);
 
 /* Host buffers of the optional outputs.  The reference's optimize_gate allocates state_history, lambda_history and
@@ -337,7 +350,11 @@ int qgd_eval_batch(qgd_handle h, const double *pcofs, int32_t n_members, int32_t
  * form of the gradient scalars on the N > 64 path 0..3 or -1, block Gauss-Jordan inverse in use 0/1, windows of the time
  * grid), "small_path" (1 value: whether the last evaluation ran on the small-problem path of qgd_set_small_path), "front_path"
  * (1 value: whether the last forward evaluation took the fused front, below), "batch_path" (1 value: whether the last
- * qgd_eval_batch call ran its members side by side, 1, or one after another, 0).  Returns the number of doubles the buffer needs
+ * qgd_eval_batch call ran its members side by side, 1, or one after another, 0), "column_overlaps" ([n_cols][2]: the overlaps
+ * (a_j, b_j) = (<w_j,R_j>, <w_j,T_j>) of every column of the stored sweep's final state with the handle's target, for any cost
+ * type; after a small-path evaluation the forward sweep is redone on the general path, as for "P"; QGD_ERR_STATE without a
+ * target or without a stored sweep -- none yet, or a batch since --, QGD_ERR_UNSUPPORTED on a windowed grid, a partitioned
+ * handle or one with a communicator).  Returns the number of doubles the buffer needs
  * through *needed when out == NULL.
  *
  * The fused front (N = 64 with sparse operators, Hermite order <= 8, 513 .. 704 time points, one rank, the grid resident, a

@@ -438,9 +438,10 @@ function hip_objective(prob::SchrodingerProb, controls, pcof::Vector{Float64}, t
     return objective_terms(dp.last_out3, prob.N_ess_levels)
 end
 
-"cost_type as in src/eval_grad_discrete_adjoint.jl:26-35; anything else throws like the reference."
+"cost_type as in src/eval_grad_discrete_adjoint.jl:26-35, and :StateTransfer (the per-column infidelity 1 - mean_j |t_j' psi_j|^2,
+include/qgd.h); anything else throws like the reference."
 function set_cost_type!(dp, cost_type)
-    code = cost_type == :Infidelity ? 0 : cost_type == :Tracking ? 1 : cost_type == :Norm ? 2 : throw("Invalid cost type: $cost_type")
+    code = cost_type == :Infidelity ? 0 : cost_type == :Tracking ? 1 : cost_type == :Norm ? 2 : cost_type == :StateTransfer ? 3 : throw("Invalid cost type: $cost_type")
     dp.cost_type == cost_type && return
     check(dp.handle, ccall((:qgd_set_cost_type, libqgd), Cint, (Ptr{Cvoid}, Int32), dp.handle, code))
     dp.cost_type = cost_type

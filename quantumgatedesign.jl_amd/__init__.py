@@ -18,7 +18,7 @@ from .evolution import (DeviceProblem, device_problem, clear_cache, release, eva
                         get_populations, eval_populations, subsystem_population_map, eval_expectations, observable_planes, eval_pullback, pullback_cotangents,
                         eval_dense, hermite_interpolate, hermite_dense_weights, dense_times, eval_dense_pullback,
                         discrete_adjoint_batch, eval_objective_batch, batch_pcofs, finite_difference_points, finite_difference_quotient,
-                        discrete_adjoint_, infidelity, infidelity_real, guard_penalty_real, complex_to_real,
+                        discrete_adjoint_, infidelity, infidelity_real, state_transfer_infidelity, COST_TYPES, guard_penalty_real, complex_to_real,
                         real_to_complex)
 from .distributed import (DeviceBackend, TimePartitioned, TorchComm, LocalGroup, ColumnBackend, ColumnSharded,
                           RcclEvaluation, comm_unique_id)

@@ -28,7 +28,8 @@ static inline const char *qgd_path(const char *key)
 typedef struct qgdk_ctx {
     int N, Np, c, cp, n_ops, n_ess, m, nt, n_pcof, nc_max;
     int have_guard, have_target, inv_batch;
-    int cost_type;      // 0 :Infidelity, 1 :Tracking, 2 :Norm (eval_grad_discrete_adjoint.jl:26-35); the kernels get have_target * (1 + cost_type)
+    int cost_type;      // 0 :Infidelity, 1 :Tracking, 2 :Norm (eval_grad_discrete_adjoint.jl:26-35), 3 :StateTransfer (per-column fidelity, DESIGN.md
+                        // section 4k); the kernels get have_target * (1 + cost_type)
     double dt, tf;
     hipStream_t stream;
     // device buffers
@@ -69,7 +70,9 @@ typedef struct qgdk_ctx {
     double *scal;       // [4]: <w,R>, <w,T>, guard, spare
     double *gpart;      // per-workgroup partial guard penalties, added in index order by the terminal stage (gpart_on: single GPU, resident grid)
     int gpart_on, gpart_n, gpart_terminal;   // gpart_terminal: the terminal stage of this handle adds the partials up (else qgdk_guard_fold does)
-    double *term_part;  // [2 * 1024 + 1]: per-workgroup partial overlaps of k_terminal_sum and its ticket counter (zeroed at creation)
+    double *term_part;  // [qgdk_term_part_len]: per-workgroup partial overlaps of k_terminal_sum, its ticket counter (zeroed at creation), then the
+                        // per-column partials of k_terminal_cols_sum
+    double *colab;      // [cp][2]: per-column overlaps (a_j, b_j) of the :StateTransfer terminal stage and of qgdk_column_overlaps
     double *cw;         // [2*(m+1)]: c_j dt^j, c_j (-dt)^j
     double *binv;       // work space of the block Gauss-Jordan inverse for N > 64 (qgdk_dense_inverse), or null
     double *inv_scratch;
@@ -176,6 +179,8 @@ int qgdk_guard_parts(const qgdk_ctx *c);      /* workgroups of the guard stage o
 int qgdk_guard_fold(const qgdk_ctx *c);       /* scal[2] += the partials of gpart in a fixed order (windows, ranks without the final time) */
 int qgdk_terminal_can_fuse(const qgdk_ctx *c);
 int qgdk_terminal(const qgdk_ctx *c, int write_y);
+size_t qgdk_term_part_len(int Np, int cp);
+int qgdk_column_overlaps(const qgdk_ctx *c);  /* colab = the per-column overlaps of the stored final state with the target */
 int qgdk_terminal_given(const qgdk_ctx *c);   /* y_N from the overlaps already in scal (column shards) */
 int qgdk_adjoint_blocks(const qgdk_ctx *c);
 int qgdk_adjoint_finish(const qgdk_ctx *c);

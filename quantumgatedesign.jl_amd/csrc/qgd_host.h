@@ -394,6 +394,9 @@ inline int refuse_reuse(qgd_handle h, int history_precomputed)
     } while (0)
 
 
+// :StateTransfer divides by the GLOBAL column count, which a column shard does not know
+#define COLUMN_SHARD_STATE_TRANSFER "cost type :StateTransfer is not supported on column shards (the cost is normalised by the global column count)"
+
 #define NEEDS_RESIDENT_GRID(h, what)                                                                                   \
     do { if ((h)->chunks_eff > 1) return fail((h), QGD_ERR_UNSUPPORTED, std::string(what) + " needs the whole time grid resident: this handle " \
                                                "processes it in " + std::to_string((h)->chunks_eff) + " windows (raise qgd_set_memory_budget)"); } while (0)

@@ -516,8 +516,9 @@ int qgd_create(const qgd_problem_desc *d, qgd_handle *out)
     CREATE_TRY(hipMemset(k.target, 0, Np * PWc * sizeof(double)));
     CREATE_RC(dev_alloc(h, h->static_bufs, &h->scal_static, (size_t)8));
     k.scal = h->scal_static;
-    CREATE_RC(dev_alloc(h, h->static_bufs, &k.term_part, (size_t)2 * 1024 + 2));
+    CREATE_RC(dev_alloc(h, h->static_bufs, &k.term_part, qgdk_term_part_len((int)Np, k.cp)));
     (void)hipMemset(k.term_part, 0, ((size_t)2 * 1024 + 2) * sizeof(double));       // (the ticket counter behind the partial sums)
+    CREATE_RC(dev_alloc(h, h->static_bufs, &k.colab, (size_t)2 * k.cp));
     CREATE_RC(dev_alloc(h, h->static_bufs, &k.cw, (size_t)2 * 20));
     CREATE_RC(dev_alloc(h, h->static_bufs, &k.status, (size_t)4));      // [singular flag | matrices redone | N = 64: of these, by the last resort | N = 64: first attempt (qgd_inverse_cb.h)]
     h->status_static = k.status;
@@ -623,8 +624,8 @@ int qgd_set_target(qgd_handle h, const double *target_real)
 int qgd_set_cost_type(qgd_handle h, int32_t cost_type)
 {
     if (!h) return fail(h, QGD_ERR_ARGUMENT, "null handle");
-    if (cost_type < QGD_COST_INFIDELITY || cost_type > QGD_COST_NORM)
-        return fail(h, QGD_ERR_ARGUMENT, "Invalid cost type (0 :Infidelity, 1 :Tracking, 2 :Norm)");    // the reference throws "Invalid cost type"
+    if (cost_type < QGD_COST_INFIDELITY || cost_type > QGD_COST_STATE_TRANSFER)
+        return fail(h, QGD_ERR_ARGUMENT, "Invalid cost type (0 :Infidelity, 1 :Tracking, 2 :Norm, 3 :StateTransfer)");    // the reference throws "Invalid cost type"
     if (h->k.cost_type == cost_type) return QGD_OK;      // (a shim that sets it on every call must not cost a captured graph)
     drop_graph(h);
     h->k.cost_type = cost_type;

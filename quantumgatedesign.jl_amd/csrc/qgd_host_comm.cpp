@@ -181,6 +181,7 @@ int comm_discrete_adjoint(qgd_handle h, const double *pcof, int n_pcof, int hist
     // what every rank gets alike is refused before anything is launched (no collective is left half-entered)
     if (pcof && n_pcof != h->k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
     if (!pcof && !h->have_tables && h->k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
+    if (h->comm_shard != QGD_SHARD_TIME && h->k.cost_type == QGD_COST_STATE_TRANSFER) return fail(h, QGD_ERR_UNSUPPORTED, COLUMN_SHARD_STATE_TRANSFER);
     if (int rc = refuse_reuse(h, history_precomputed)) return rc;
     return comm_local_error(h, comm_discrete_adjoint_body(h, pcof, n_pcof, history_precomputed, grad, uv_history, lambda_history, adjoint_forcing, out3));
 }
@@ -231,6 +232,7 @@ int comm_eval_forward(qgd_handle h, const double *pcof, int n_pcof, double *uv_h
     if (pcof && n_pcof != h->k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
     if (pcof && !h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before passing pcof");
     if (!pcof && !h->have_tables && h->k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
+    if (h->comm_shard != QGD_SHARD_TIME && h->k.cost_type == QGD_COST_STATE_TRANSFER) return fail(h, QGD_ERR_UNSUPPORTED, COLUMN_SHARD_STATE_TRANSFER);
     return comm_local_error(h, comm_eval_forward_body(h, pcof, n_pcof, uv_history, out3));
 }
 

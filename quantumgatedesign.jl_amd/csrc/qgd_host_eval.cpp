@@ -768,6 +768,7 @@ int qgd_get_intermediate(qgd_handle h, const char *name, double *out, size_t cap
     else if (s == "small_path") need = 1;
     else if (s == "front_path") need = 1;
     else if (s == "batch_path") need = 1;
+    else if (s == "column_overlaps") need = (size_t)k.c * 2;
     else return fail(h, QGD_ERR_ARGUMENT, "unknown intermediate '" + s + "'");
     if (needed) *needed = need;
     if (!out) return QGD_OK;
@@ -781,6 +782,12 @@ int qgd_get_intermediate(qgd_handle h, const char *name, double *out, size_t cap
         out[2] = (k.dense_gemm && k.binv) ? 1.0 : 0.0;               // block Gauss-Jordan inverse over 64-column blocks
         out[3] = (double)h->chunks_eff;
         return QGD_OK;
+    }
+    if (s == "column_overlaps") {      // refused from the handle's state alone, before anything is launched
+        if (h->chunks_eff > 1 || h->part_world != 1 || k.part_world != 1 || h->comm)
+            return fail(h, QGD_ERR_UNSUPPORTED, "qgd_get_intermediate(\"column_overlaps\") needs the whole time grid resident on one handle");
+        if (!k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called before qgd_get_intermediate(\"column_overlaps\")");
+        if (h->sweep.kind == SWEEP_NONE) return fail(h, QGD_ERR_STATE, "no stored forward sweep for qgd_get_intermediate(\"column_overlaps\") (none yet, or a batch since)");
     }
     NEEDS_RESIDENT_GRID(h, "qgd_get_intermediate");
     const bool matrices = s == "L" || s == "R" || s == "Linv" || s == "P";
@@ -810,6 +817,12 @@ int qgd_get_intermediate(qgd_handle h, const char *name, double *out, size_t cap
             HIP_TRY(h, hipMemcpy(pl_.data(), k.sigma + (size_t)g * need, need * sizeof(double), hipMemcpyDeviceToHost));
             for (size_t e = 0; e < need; e++) out[e] += pl_[e];
         }
+        return QGD_OK;
+    }
+    if (s == "column_overlaps") {      // (a_j, b_j) of the stored final state against the target, whatever the cost type
+        K_TRY(h, qgdk_column_overlaps(&k));
+        HIP_TRY(h, hipMemcpyAsync(out, k.colab, need * sizeof(double), hipMemcpyDeviceToHost, k.stream));
+        HIP_TRY(h, hipStreamSynchronize(k.stream));
         return QGD_OK;
     }
     if (s == "tables") { HIP_TRY(h, hipMemcpy(out, k.tab, need * sizeof(double), hipMemcpyDeviceToHost)); return QGD_OK; }
@@ -914,6 +927,7 @@ int qgd_cols_forward(qgd_handle h, const double *pcof, int32_t n_pcof)
     ENTER(h, ENTER_KEEPS_GRAPH);
     if (!h->k.have_target) return fail(h, QGD_ERR_STATE, "qgd_set_target must be called first");
     if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called first");
+    if (h->k.cost_type == QGD_COST_STATE_TRANSFER) return fail(h, QGD_ERR_UNSUPPORTED, COLUMN_SHARD_STATE_TRANSFER);
     return run_forward(h, pcof, n_pcof);        // scal = this rank's <w,R>, <w,T>, guard: exchange buffer 3
 }
 
@@ -922,6 +936,7 @@ int qgd_cols_adjoint(qgd_handle h, int32_t keep_scalars)
 {
     ENTER(h, ENTER_KEEPS_GRAPH | ENTER_NO_GRID);
     qgdk_ctx &k = h->k;
+    if (k.cost_type == QGD_COST_STATE_TRANSFER) return fail(h, QGD_ERR_UNSUPPORTED, COLUMN_SHARD_STATE_TRANSFER);
     if (!sweep_stored(h)) return fail(h, QGD_ERR_STATE, "no forward evaluation to differentiate (qgd_cols_forward first)");
     { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal_given(&k)); }      // y_N from the all-reduced overlaps
     int rc;

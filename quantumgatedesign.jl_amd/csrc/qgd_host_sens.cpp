@@ -81,14 +81,34 @@ static void target_overlaps(qgd_handle h, const double *s, double &sR, double &s
 }
 
 
+// the same column by column (:StateTransfer): sR[col], sT[col] = <s_col,R_col>, <s_col,T_col>
+static void column_target_overlaps(qgd_handle h, const double *s, double *sR, double *sT)
+{
+    const size_t N = h->k.N, c = h->k.c;
+    const double *R = h->target_host.data();
+    for (size_t col = 0; col < c; col++) {
+        double aR = 0.0, aT = 0.0;
+        for (size_t i = 0; i < N; i++) {
+            const size_t e = i + 2 * N * col;
+            const double sre = s[e], sim = s[N + e], rre = R[e], rim = R[N + e];
+            aR += sre * rre + sim * rim;
+            aT += sre * rim - sim * rre;
+        }
+        sR[col] = aR; sT[col] = aT;
+    }
+}
+
+
 // The terminal part of the forced gradient from s_N, the sensitivities of the final state to every parameter (sN_dev: panels
 // with parameter p in columns p * cp ..), plus the guard part the forced sweeps accumulated in fs_gacc (grad may be NULL):
 //   :Infidelity  -(2/N_ess^2) (<w_N,R> <s_N,R> + <w_N,T> <s_N,T>)
 //   :Tracking    d(0.5 |w_N - R|^2) = <s_N, w_N - R>;  :Norm  d(0.5 |w_N|^2) = <s_N, w_N>  (eval_grad_forced.jl:160-163)
+//   :StateTransfer  -(2/c) sum_j (a_j <s_j,R_j> + b_j <s_j,T_j>) with the overlaps a_j, b_j of column j of w_N
 // Also returns what the Hessian's terminal part is made of: the overlaps, and with keep_s s_N itself as [2N x c] per parameter.
 struct ForcedTerminal {
     double f = 0.0;                 // -2 / N_ess^2
     std::vector<double> sR, sT;     // <s_N,R>, <s_N,T> of every parameter
+    std::vector<double> cR, cT;     // (:StateTransfer; f is then -2 / c) the same column by column: parameter p, column j at p * c + j
     std::vector<double> s;          // (keep_s) s_N of parameter p at p * 2N * c
 };
 
@@ -98,23 +118,34 @@ static int forced_terminal(qgd_handle h, const double *sN_dev, double *grad, For
     const size_t np = (size_t)k.n_pcof, N = k.N, L = 2 * N * k.c, hstep = (size_t)k.Np * 2 * k.cp, PWs = 2 * np * k.cp;
     std::vector<double> sN((size_t)k.Np * PWs), gacc(np), scal(4), d, s_one(L);
     HIP_TRY(h, hipMemcpy(sN.data(), sN_dev, sN.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if (k.cost_type) {     // :Tracking / :Norm need the final state itself: d = w_N - R, or w_N
+    const bool per_col = k.cost_type == QGD_COST_STATE_TRANSFER;
+    const size_t nc = (size_t)k.c;
+    std::vector<double> wa(per_col ? nc : 0), wb(per_col ? nc : 0);
+    if (k.cost_type) {     // :Tracking / :Norm need the final state itself: d = w_N - R, or w_N; :StateTransfer its column overlaps
         std::vector<double> wN(hstep);
         HIP_TRY(h, hipMemcpy(wN.data(), k.hist + ((size_t)k.nt - 1) * hstep, hstep * sizeof(double), hipMemcpyDeviceToHost));
         d.resize(L);
         unpack_panel(d.data(), 2 * N, wN.data(), 2 * k.cp, k.N, k.c);
         if (k.cost_type == QGD_COST_TRACKING) for (size_t e = 0; e < L; e++) d[e] -= h->target_host[e];
+        if (per_col) column_target_overlaps(h, d.data(), wa.data(), wb.data());
     }
     HIP_TRY(h, hipMemcpy(gacc.data(), k.fs_gacc, sizeof(double) * np, hipMemcpyDeviceToHost));
     HIP_TRY(h, hipMemcpy(scal.data(), k.scal, 3 * sizeof(double), hipMemcpyDeviceToHost));
     const double a = scal[0], b = scal[1];
-    t.f = -2.0 / ((double)k.n_ess * k.n_ess);
+    t.f = per_col ? -2.0 / (double)k.c : -2.0 / ((double)k.n_ess * k.n_ess);
     t.sR.assign(np, 0.0); t.sT.assign(np, 0.0); t.s.assign(keep_s ? np * L : 0, 0.0);
+    t.cR.assign(per_col ? np * nc : 0, 0.0); t.cT.assign(per_col ? np * nc : 0, 0.0);
     for (size_t p = 0; p < np; p++) {
         double *s = keep_s ? t.s.data() + p * L : s_one.data();
         unpack_panel(s, 2 * N, sN.data() + 2 * p * k.cp, (int)PWs, k.N, k.c);
         target_overlaps(h, s, t.sR[p], t.sT[p]);
         double sW = 0.0;
+        if (per_col) {
+            column_target_overlaps(h, s, t.cR.data() + p * nc, t.cT.data() + p * nc);
+            for (size_t col = 0; col < nc; col++) sW += wa[col] * t.cR[p * nc + col] + wb[col] * t.cT[p * nc + col];
+            if (grad) grad[p] = t.f * sW + gacc[p];
+            continue;
+        }
         for (size_t col = 0; k.cost_type && col < (size_t)k.c; col++)
             for (size_t i = 0; i < N; i++) {
                 const size_t e = i + 2 * N * col;
@@ -173,7 +204,8 @@ static int hvp_buffers(qgd_handle h)
 
 
 // Phi'' s_v(N) as the terminal part of the second-order adjoint's right-hand side F = -f, in panel layout:
-//   :Infidelity  +(2/N_ess^2) (<s_v,R> R + <s_v,T> T);   :Tracking / :Norm  -s_v(N)
+//   :Infidelity  +(2/N_ess^2) (<s_v,R> R + <s_v,T> T);   :Tracking / :Norm  -s_v(N);
+//   :StateTransfer  +(2/c) (<s_j,R_j> R_j + <s_j,T_j> T_j) column by column
 static int hvp_terminal(qgd_handle h, const double *svN_dev, double *term_dev)
 {
     qgdk_ctx &k = h->k;
@@ -182,14 +214,18 @@ static int hvp_terminal(qgd_handle h, const double *svN_dev, double *term_dev)
     HIP_TRY(h, hipMemcpyAsync(sN.data(), svN_dev, hstep * sizeof(double), hipMemcpyDeviceToHost, k.stream));
     HIP_TRY(h, hipStreamSynchronize(k.stream));
     unpack_panel(s.data(), 2 * N, sN.data(), (int)PWc, k.N, k.c);
-    if (k.cost_type) {
+    if (k.cost_type && k.cost_type != QGD_COST_STATE_TRANSFER) {
         for (size_t e = 0; e < L; e++) t[e] = -s[e];
     } else {
-        double sR, sT;
-        target_overlaps(h, s.data(), sR, sT);
-        const double f = 2.0 / ((double)k.n_ess * k.n_ess);
+        const bool per_col = k.cost_type == QGD_COST_STATE_TRANSFER;
+        std::vector<double> cR(k.c), cT(k.c);
+        double sR = 0.0, sT = 0.0;
+        if (per_col) column_target_overlaps(h, s.data(), cR.data(), cT.data());
+        else target_overlaps(h, s.data(), sR, sT);
+        const double f = per_col ? 2.0 / (double)k.c : 2.0 / ((double)k.n_ess * k.n_ess);
         for (size_t col = 0; col < (size_t)k.c; col++)
             for (size_t i = 0; i < N; i++) {
+                if (per_col) { sR = cR[col]; sT = cT[col]; }
                 const size_t e = i + 2 * N * col;
                 const double rre = h->target_host[e], rim = h->target_host[N + e];
                 t[e] = f * (sR * rre + sT * rim);            // T = [R_im; -R_re]
@@ -369,9 +405,10 @@ int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *h
     { PhaseTimer t(h, "hess_terms"); K_TRY(h, qgdk_hess_kernels(&k, b.shist, b.Z, b.half, b.slab, b.zt, b.Y)); }
     if (k.have_guard) { PhaseTimer t(h, "hess_guard"); K_TRY(h, qgdk_hess_gram(&k, b.shist, b.ws, gpartial, Gm)); }
     if ((rc = check_status(h))) return rc;
-    // terminal part: the overlaps <s_N,R>, <s_N,T> of every parameter (:Infidelity) or s_N itself (:Tracking / :Norm)
+    // terminal part: the overlaps <s_N,R>, <s_N,T> of every parameter (:Infidelity; per column for :StateTransfer) or s_N itself (:Tracking / :Norm)
     ForcedTerminal t;
-    if ((rc = forced_terminal(h, b.shist + (nt - 1) * hstepS, grad, t, k.cost_type != 0))) return rc;
+    const bool local_cost = k.cost_type == QGD_COST_TRACKING || k.cost_type == QGD_COST_NORM;
+    if ((rc = forced_terminal(h, b.shist + (nt - 1) * hstepS, grad, t, local_cost))) return rc;
     std::vector<double> Yh(np * np), Gh(np * np);
     HIP_TRY(h, hipMemcpy(Yh.data(), b.Y, np * np * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(h, hipMemcpy(Gh.data(), Gm, np * np * sizeof(double), hipMemcpyDeviceToHost));
@@ -379,9 +416,13 @@ int qgd_eval_hessian(qgd_handle h, const double *pcof, int32_t n_pcof, double *h
     for (size_t p = 0; p < np; p++)
         for (size_t q = 0; q < np; q++) {
             double phi;
-            if (k.cost_type) {
+            if (local_cost) {
                 phi = 0.0;
                 for (size_t e = 0; e < L; e++) phi += t.s[p * L + e] * t.s[q * L + e];
+            } else if (k.cost_type == QGD_COST_STATE_TRANSFER) {      // the :Infidelity expression per column, summed over the columns, with -2/c
+                phi = 0.0;
+                for (size_t j = 0; j < (size_t)k.c; j++) phi += t.cR[p * k.c + j] * t.cR[q * k.c + j] + t.cT[p * k.c + j] * t.cT[q * k.c + j];
+                phi *= t.f;
             } else {
                 phi = t.f * (t.sR[p] * t.sR[q] + t.sT[p] * t.sT[q]);
             }

@@ -80,14 +80,14 @@ struct ChainArgs {
     const double *suf_P, *suf_phi; int suf_n;
     // MODE 2, t_on: ONE extra workgroup (the last of the grid) does the work of k_terminal -- overlaps <w_N,R>, <w_N,T>
     // and y_N -- beside the affine parts of the blocks, which do not need it: the adjoint sweep starts one launch earlier
-    int t_on, t_nt, t_ness, t_have_target;
+    int t_on, t_nt, t_ness, t_have_target;      // (:StateTransfer: t_ness is the column count c, terminal_norm)
     const double *t_hist, *t_target, *t_forcing, *t_ytarget;
     // MODE 0, p0_on (fused front, qgd_front.h): ONE extra workgroup (the last of the grid) forms phi_0 = L_0 psi_0 from the panel
     // of L_0^H beside the block products, which do not need it (the history pass, two launches later, starts from it)
     int p0_on;
     const double *p0_E, *p0_psi0;
     double *p0_out;
-    double *t_yhist, *t_scal, *t_y2, *t_y3, *t_y4;
+    double *t_yhist, *t_scal, *t_y2, *t_y3, *t_y4, *t_colab;
 };
 
 __device__ __forceinline__ void terminal_block(const double *__restrict__ hist, const double *__restrict__ target,
@@ -95,7 +95,7 @@ __device__ __forceinline__ void terminal_block(const double *__restrict__ hist, 
                                                double *__restrict__ scal, int Np, int cp, int nt, int n_ess, int have_target,
                                                int write_y, double *__restrict__ y2, double *__restrict__ y3,
                                                double *__restrict__ y4, int given_ab, const double *gpart = nullptr, int gpart_n = 0,
-                                               const double *ytarget = nullptr);
+                                               const double *ytarget = nullptr, double *colab = nullptr);
 
 // phi_0 = L_0 psi_0 = E^H psi_0 (E = L_0^H, panel layout) as one MFMA product: the left operand is read the way the adjoint
 // sweep reads a step matrix (P^H from the panel of P), all 32 fragment loads of a wave in flight at once; waves 0-3 of the
@@ -227,7 +227,7 @@ __device__ __forceinline__ void chain_fast_body(const ChainArgs &a, const int bi
     if (MODE == 0 && a.p0_on && bid == nbid - 1) { phi0_block(a.p0_E, a.p0_psi0, a.p0_out, a.cp); return; }
     if (MODE == 2 && a.t_on && bid == nbid - 1) {      // the extra workgroup: k_terminal's work
         terminal_block(a.t_hist, a.t_target, a.t_forcing, a.t_yhist, a.t_scal, NP, a.cp, a.t_nt, a.t_ness, a.t_have_target, 1,
-                       a.t_y2, a.t_y3, a.t_y4, 0, a.t_gpart, a.t_gpart_n, a.t_ytarget);
+                       a.t_y2, a.t_y3, a.t_y4, 0, a.t_gpart, a.t_gpart_n, a.t_ytarget, a.t_colab);
         return;
     }
     int b, grp0;
@@ -1252,6 +1252,45 @@ __global__ __launch_bounds__(256) void k_guard_diag(const double *__restrict__ w
 // eval_grad_discrete_adjoint.jl:22-40).  Single workgroup.
 //   scal[0] = <w_N,R>, scal[1] = <w_N,T>;  y_N = (2/Ness^2)(a R + b T) + f_N
 // ---------------------------------------------------------------------------
+// Per-column overlaps a_j = <w_j,R_j>, b_j = <w_j,T_j>, T_j = [R_im; -R_re] (infidelity.jl:13-17 column by column), of the
+// panel w against the panel `target`, into colab[2 j], colab[2 j + 1] for every padded column j < cp.  One workgroup of whole
+// waves.  Wave q takes the column groups q, q + nw, ...; in a group lane l owns column l & 7 and adds the rows l >> 3,
+// (l >> 3) + 8, ... in ascending order, reading the re slot and the im slot (8 further) of its column; the eight row classes
+// of a column are then added by a shuffle tree.  No element is strided over by thread index, so the order of every sum is the
+// same whatever 2 cp is against the workgroup size, and the same on every run.  Padded rows and columns hold zeros in `target`.
+__device__ __forceinline__ void column_overlaps_block(const double *__restrict__ w, const double *__restrict__ target,
+                                                      double *colab, int Np, int cp)
+{
+    const int PWc = 2 * cp, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6, jj = lane & 7;
+    for (int g = wave; g < cp / 8; g += nw) {
+        double a = 0.0, b = 0.0;
+        for (int r = lane >> 3; r < Np; r += 8) {
+            const size_t e = (size_t)r * PWc + g * 16 + jj;
+            const double u = w[e], v = w[e + 8], tr = target[e], ti = target[e + 8];
+            a += u * tr + v * ti;
+            b += u * ti - v * tr;
+        }
+        for (int off = 32; off >= 8; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
+        if (lane < 8) { colab[2 * (g * 8 + jj)] = a; colab[2 * (g * 8 + jj) + 1] = b; }
+    }
+}
+
+// J = 1 - (1/c) sum_{j < c} (a_j^2 + b_j^2) from colab, by the whole workgroup in a fixed order: thread t adds the columns
+// t, t + blockDim, ... ascending, then the shuffle tree and the waves in order.  red: 16 doubles of LDS.  Every thread must
+// call it (barriers); the value is returned to thread 0.
+__device__ __forceinline__ double state_transfer_cost(const double *colab, int c, double *red)
+{
+    double s = 0.0;
+    for (int j = threadIdx.x; j < c; j += blockDim.x) { const double a = colab[2 * j], b = colab[2 * j + 1]; s += a * a + b * b; }
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    s = 0.0;
+    for (int q = 0; q < (int)(blockDim.x >> 6); q++) s += red[q];
+    return 1.0 - s / (double)c;
+}
+
 // the overlaps and the terminal condition of the adjoint (infidelity.jl:7-18; eval_grad_discrete_adjoint.jl:1-67 in the
 // variable y = L^T lambda): one workgroup, any size up to 1024 threads
 __device__ __forceinline__ void terminal_block(const double *__restrict__ hist, const double *__restrict__ target,
@@ -1259,7 +1298,7 @@ __device__ __forceinline__ void terminal_block(const double *__restrict__ hist, 
                                                double *__restrict__ scal, int Np, int cp, int nt, int n_ess, int have_target,
                                                int write_y, double *__restrict__ y2, double *__restrict__ y3,
                                                double *__restrict__ y4, int given_ab, const double *gpart, int gpart_n,
-                                               const double *ytarget)
+                                               const double *ytarget, double *colab)
 {
     // ytarget (fused front, qgd_front.h): the terminal value is lambda_N = L_N^-H rhs_N itself -- the overlaps are taken with
     // `target`, the state is formed from ytarget = L_N^-H target (:Tracking / :Norm: L_N^-H rhs) and `forcing` = h = L^-H f
@@ -1270,9 +1309,14 @@ __device__ __forceinline__ void terminal_block(const double *__restrict__ hist, 
     const double *w = hist + (size_t)(nt - 1) * hstep;
     // have_target: 0 none, 1 :Infidelity, 2 :Tracking, 3 :Norm (eval_grad_discrete_adjoint.jl:26-35).  The last two are
     // local in the columns: scal[0] = 0.5 |w_N - R|^2 (0.5 |w_N|^2), scal[1] = 0, y_N = -(w_N - R) + f_N (-w_N + f_N).
+    // 4 :StateTransfer: one overlap pair per column (colab), scal[0] = J = 1 - (1/c) sum_j (a_j^2 + b_j^2), scal[1] = 0,
+    // y_N = (2/c)(a_j R_j + b_j T_j) + f_N column by column; n_ess carries c (terminal_norm).  Linear in the target like
+    // :Infidelity: the fused front's ytarget = L_N^-H target takes the target's place in y_N.
     const int cost = have_target > 1 ? have_target - 1 : 0;
     double a = 0.0, b = 0.0;
-    if (cost) {
+    if (cost == 3) {
+        column_overlaps_block(w, target, colab, Np, cp);
+    } else if (cost) {
         for (int e = threadIdx.x; e < (int)hstep; e += blockDim.x) {
             const double d = (cost == 1) ? w[e] - target[e] : w[e];
             a += 0.5 * d * d;
@@ -1301,6 +1345,23 @@ __device__ __forceinline__ void terminal_block(const double *__restrict__ hist, 
     if (gpart && threadIdx.x == 0) { gs = 0.0; for (int q = 0; q < nw; q++) gs += gred[q]; scal[2] = gs; }
     // column shards: the overlaps are GLOBAL sums over all columns (infidelity.jl:13-17); after the ranks' all-reduce
     // they are in scal and the terminal condition is formed from them, not from this rank's columns
+    if (cost == 3) {      // (the barrier above: every wave's colab entries are written)
+        const double J = state_transfer_cost(colab, n_ess, red);
+        if (threadIdx.x == 0) { scal[0] = J; scal[1] = 0.0; }
+        if (!write_y) return;
+        const double sc = 2.0 / (double)n_ess;
+        double *y = yhist + (size_t)(nt - 1) * hstep;
+        const double *f = forcing + (size_t)(nt - 1) * hstep;
+        if (ytarget) target = ytarget;
+        for (int e = threadIdx.x; e < (int)hstep; e += blockDim.x) {
+            const int col = e % PWc, c16 = col & 15, j = (col >> 4) * 8 + (col & 7);
+            const double tv = target[e], tp = target[e ^ 8];
+            const double Tv = (c16 < 8) ? tp : -tp;
+            const double v = sc * (colab[2 * j] * tv + colab[2 * j + 1] * Tv) + f[e];
+            y[e] = v; y2[e] = v; y3[e] = v; y4[e] = v;
+        }
+        return;
+    }
     if (given_ab) { a = scal[0]; b = scal[1]; }       // (a column shard's Tracking / Norm cost was reduced like the overlaps)
     else if (threadIdx.x == 0) { scal[0] = a; scal[1] = b; }
     if (!write_y) return;
@@ -1551,9 +1612,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     }
     if (last) {
         // cost 0 (:Infidelity): U = X_N target, lambda_N = (2/N_ess^2)(a + ib) U + h_N; :Tracking / :Norm: the terminal right-hand
-        // side is local, -(psi_N - target) / -psi_N (eval_grad_discrete_adjoint.jl:26-35): U = X_N rhs, lambda_N = U + h_N
+        // side is local, -(psi_N - target) / -psi_N (eval_grad_discrete_adjoint.jl:26-35): U = X_N rhs, lambda_N = U + h_N;
+        // cost 3 (:StateTransfer) is linear in the target like cost 0, with one (a_j + i b_j) per column: U = X_N target
         __syncthreads();
-        if (cost == 0) {
+        if (cost == 0 || cost == 3) {
             for (int e = threadIdx.x; e < NPC * 16; e += 256) bs[e] = target[(size_t)(e >> 4) * PWc + grp * 16 + (e & 15)];
         } else {
             #pragma unroll
@@ -1615,13 +1677,68 @@ __global__ __launch_bounds__(256) void k_terminal_sum(const double *__restrict__
     *ticket = 0;                                                  // for the next evaluation (same stream: ordered)
 }
 
+// :StateTransfer in two launches: workgroup (g, rb) takes column group g and the rows [64 rb, 64 rb + 64): thread t owns
+// column t & 7 and the rows 64 rb + (t >> 3), + 32 (ascending), the eight row classes of a wave are added by a shuffle tree,
+// the four waves in order, and the sixteen sums are STORED at part[(rb * groups + g) * 16 ..].  The workgroup that draws the
+// last ticket adds, for every column, the partials of the row blocks in index order into colab and forms J from colab in
+// state_transfer_cost's fixed order: the same bits whichever workgroup that is.  The partials lie behind k_terminal_sum's
+// own (part + 2 * 1024 + 2; qgdk_term_part_len sizes the buffer), the ticket is the same one.
+#define QGD_TERM_COL_ROWS 64
+__global__ __launch_bounds__(256) void k_terminal_cols_sum(const double *__restrict__ w, const double *__restrict__ target,
+                                                           double *__restrict__ scal, int Np, int cp, int c, double *part, double *colab,
+                                                           const double *__restrict__ gpart, int gpart_n)
+{
+    __shared__ double red[64];
+    __shared__ int last;
+    const int PWc = 2 * cp, g = blockIdx.x, rb = blockIdx.y, ng = gridDim.x, jj = threadIdx.x & 7, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double *cpart = part + 2 * 1024 + 2;
+    double a = 0.0, b = 0.0;
+    for (int r = QGD_TERM_COL_ROWS * rb + (threadIdx.x >> 3); r < min(Np, QGD_TERM_COL_ROWS * (rb + 1)); r += 32) {
+        const size_t e = (size_t)r * PWc + g * 16 + jj;
+        const double u = w[e], v = w[e + 8], tr = target[e], ti = target[e + 8];
+        a += u * tr + v * ti;
+        b += u * ti - v * tr;
+    }
+    for (int off = 32; off >= 8; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
+    if (lane < 8) { red[wave * 16 + 2 * jj] = a; red[wave * 16 + 2 * jj + 1] = b; }
+    __syncthreads();
+    int *ticket = reinterpret_cast<int *>(part + 2 * 1024);
+    if (threadIdx.x < 16) cpart[((size_t)rb * ng + g) * 16 + threadIdx.x] = ((red[threadIdx.x] + red[16 + threadIdx.x]) + red[32 + threadIdx.x]) + red[48 + threadIdx.x];
+    __threadfence();                                              // release: the partial sums before the ticket
+    __syncthreads();
+    if (threadIdx.x == 0) last = (atomicAdd(ticket, 1) == (int)(gridDim.x * gridDim.y) - 1) ? 1 : 0;
+    __syncthreads();
+    if (!last) return;
+    __threadfence();                                              // acquire: every other workgroup's partial sums
+    for (int q = threadIdx.x; q < 2 * cp; q += 256) {             // entry q of colab: column q >> 1, a or b
+        const int j = q >> 1;
+        double s = 0.0;
+        for (int r = 0; r < (int)gridDim.y; r++) s += __builtin_nontemporal_load(cpart + ((size_t)r * ng + (j >> 3)) * 16 + 2 * (j & 7) + (q & 1));
+        colab[q] = s;
+    }
+    __syncthreads();
+    const double J = state_transfer_cost(colab, c, red);
+    if (threadIdx.x != 0) return;
+    scal[0] = J; scal[1] = 0.0;
+    if (gpart) { double s = 0.0; for (int q = 0; q < gpart_n; q++) s += gpart[q]; scal[2] = s; }      // guard penalty, in index order
+    *ticket = 0;                                                  // for the next evaluation (same stream: ordered)
+}
+
 __global__ __launch_bounds__(256) void k_terminal_y(const double *__restrict__ target, const double *__restrict__ f,
                                                     const double *__restrict__ scal, double *__restrict__ y,
                                                     double *__restrict__ y2, double *__restrict__ y3, double *__restrict__ y4,
-                                                    int hstep, int PWc, int n_ess, int cost, const double *__restrict__ w)
+                                                    int hstep, int PWc, int n_ess, int cost, const double *__restrict__ w,
+                                                    const double *__restrict__ colab)
 {
     const double a = scal[0], b = scal[1], sc = 2.0 / ((double)n_ess * (double)n_ess);
     for (int e = blockIdx.x * 2048 + threadIdx.x; e < min(hstep, (int)(blockIdx.x + 1) * 2048); e += 256) {
+        if (cost == 3) {      // :StateTransfer: the column's own overlaps, 2/c (n_ess carries c)
+            const int col = e % PWc, j = (col >> 4) * 8 + (col & 7);
+            const double tv = target[e], tp = target[e ^ 8];
+            const double v = (2.0 / (double)n_ess) * (colab[2 * j] * tv + colab[2 * j + 1] * (((col & 15) < 8) ? tp : -tp)) + f[e];
+            y[e] = v; y2[e] = v; y3[e] = v; y4[e] = v;
+            continue;
+        }
         if (cost) { const double v = ((cost == 1) ? target[e] - w[e] : -w[e]) + f[e]; y[e] = v; y2[e] = v; y3[e] = v; y4[e] = v; continue; }
         const int c16 = (e % PWc) & 15;
         const double tv = target[e], tp = target[e ^ 8];
@@ -1639,9 +1756,16 @@ __global__ __launch_bounds__(1024) void k_terminal(const double *__restrict__ hi
                                                   int n_ess, int have_target, int write_y,
                                                   double *__restrict__ y2, double *__restrict__ y3,
                                                   double *__restrict__ y4, int given_ab, const double *__restrict__ gpart, int gpart_n,
-                                                  const double *__restrict__ ytarget)
+                                                  const double *__restrict__ ytarget, double *colab)
 {
-    terminal_block(hist, target, forcing, yhist, scal, Np, cp, nt, n_ess, have_target, write_y, y2, y3, y4, given_ab, gpart, gpart_n, ytarget);
+    terminal_block(hist, target, forcing, yhist, scal, Np, cp, nt, n_ess, have_target, write_y, y2, y3, y4, given_ab, gpart, gpart_n, ytarget, colab);
+}
+
+// the per-column overlaps alone (qgd_get_intermediate "column_overlaps"): any cost type, any panel size
+__global__ __launch_bounds__(256) void k_column_overlaps(const double *__restrict__ w, const double *__restrict__ target,
+                                                         double *__restrict__ colab, int Np, int cp)
+{
+    column_overlaps_block(w, target, colab, Np, cp);
 }
 
 // scal[2] += the guard partials in a fixed order (thread-strided ascending sums, shuffle tree, waves in order): where no
@@ -1873,6 +1997,16 @@ int qgdk_guard_kernel(const qgdk_ctx *c)
 }
 
 static int launch_terminal(const qgdk_ctx *c, int write_y, int given_ab);
+// what the terminal kernels divide by: N_ess (squared there) for :Infidelity, the column count for :StateTransfer
+static int terminal_norm(const qgdk_ctx *c) { return c->cost_type == 3 ? c->c : c->n_ess; }
+// doubles of term_part: k_terminal_sum's partials and the ticket, then k_terminal_cols_sum's [row blocks][cp / 8][16]
+size_t qgdk_term_part_len(int Np, int cp) { return (size_t)2 * 1024 + 2 + (size_t)((Np + QGD_TERM_COL_ROWS - 1) / QGD_TERM_COL_ROWS) * 2 * cp; }
+int qgdk_column_overlaps(const qgdk_ctx *c)
+{
+    const size_t hstep = (size_t)c->Np * 2 * c->cp;
+    hipLaunchKernelGGL(k_column_overlaps, dim3(1), dim3(256), 0, c->stream, c->hist + (size_t)(c->nt - 1) * hstep, c->target, c->colab, c->Np, c->cp);
+    return (int)hipGetLastError();
+}
 int qgdk_terminal(const qgdk_ctx *c, int write_y) { return launch_terminal(c, write_y, 0); }
 int qgdk_terminal_given(const qgdk_ctx *c) { return launch_terminal(c, 1, 1); }
 static int launch_terminal(const qgdk_ctx *c, int write_y, int given_ab)
@@ -1886,23 +2020,26 @@ static int launch_terminal(const qgdk_ctx *c, int write_y, int given_ab)
         const double *w = c->hist + (size_t)(c->nt - 1) * hstep;
         if (!given_ab) {
             HIPCHK(hipMemsetAsync(c->scal, 0, 2 * sizeof(double), c->stream));
-            if (c->have_target) hipLaunchKernelGGL(k_terminal_sum, dim3(twg), dim3(256), 0, c->stream, w, c->target, c->scal, (int)hstep, 2 * c->cp, c->cost_type, c->term_part, tchunk,
+            if (c->have_target && c->cost_type == 3)
+                hipLaunchKernelGGL(k_terminal_cols_sum, dim3(c->cp / 8, (c->Np + QGD_TERM_COL_ROWS - 1) / QGD_TERM_COL_ROWS), dim3(256), 0, c->stream, w, c->target, c->scal,
+                                   c->Np, c->cp, c->c, c->term_part, c->colab, (c->gpart_on && c->gpart_terminal && c->have_guard) ? c->gpart : nullptr, c->gpart_n);
+            else if (c->have_target) hipLaunchKernelGGL(k_terminal_sum, dim3(twg), dim3(256), 0, c->stream, w, c->target, c->scal, (int)hstep, 2 * c->cp, c->cost_type, c->term_part, tchunk,
                                                    (c->gpart_on && c->gpart_terminal && c->have_guard) ? c->gpart : nullptr, c->gpart_n);
             else if (c->gpart_on && c->gpart_terminal && c->have_guard)      // no target: only the guard penalty is to be added up
                 hipLaunchKernelGGL(k_terminal, dim3(1), dim3(256), 0, c->stream, c->hist, c->target, c->forcing, c->yhist, c->scal, c->Np, c->cp, c->nt,
-                                   c->n_ess, 0, 0, y.slot, y.slot, y.slot, 0, c->gpart, c->gpart_n, (const double *)nullptr);
+                                   c->n_ess, 0, 0, y.slot, y.slot, y.slot, 0, c->gpart, c->gpart_n, (const double *)nullptr, c->colab);
         }
         if (write_y)
             hipLaunchKernelGGL(k_terminal_y, dim3(nwg), dim3(256), 0, c->stream, c->target, c->forcing + (size_t)(c->nt - 1) * hstep,
-                               c->scal, y.yhist, y.slot, y.bnd, y.bnd2, (int)hstep, 2 * c->cp, c->n_ess, c->cost_type, w);
+                               c->scal, y.yhist, y.slot, y.bnd, y.bnd2, (int)hstep, 2 * c->cp, terminal_norm(c), c->cost_type, w, c->colab);
         return (int)hipGetLastError();
     }
     // (fused front: the terminal value is lambda_N, formed from termU = L_N^-H target and h_N, into lambda's history)
     hipLaunchKernelGGL(k_terminal, dim3(1), dim3(hstep >= 32768 ? 1024 : 256), 0, c->stream, c->hist, c->target, c->front ? c->hforc : c->forcing,
                        c->front ? c->lam : c->yhist,
-                       c->scal, c->Np, c->cp, c->nt, c->n_ess, c->have_target * (1 + c->cost_type), write_y, y.slot, y.bnd, y.bnd2, given_ab,
+                       c->scal, c->Np, c->cp, c->nt, terminal_norm(c), c->have_target * (1 + c->cost_type), write_y, y.slot, y.bnd, y.bnd2, given_ab,
                        (c->gpart_on && c->gpart_terminal && c->have_guard && !given_ab) ? c->gpart : nullptr, c->gpart_n,
-                       c->front ? c->termU : (const double *)nullptr);
+                       c->front ? c->termU : (const double *)nullptr, c->colab);
     return (int)hipGetLastError();
 }
 
@@ -1917,7 +2054,7 @@ int qgdk_adjoint_blocks(const qgdk_ctx *c)
     a.forcing = c->front ? c->hforc : c->forcing; a.phi = c->phiX;
     if (c->fuse_terminal && chain_is_fast(c)) {          // y_N and the overlaps by an extra workgroup of this launch
         const YNDest y = yN_dest(c);
-        a.t_on = 1; a.t_nt = c->nt; a.t_ness = c->n_ess; a.t_have_target = c->have_target * (1 + c->cost_type);
+        a.t_on = 1; a.t_nt = c->nt; a.t_ness = terminal_norm(c); a.t_colab = c->colab; a.t_have_target = c->have_target * (1 + c->cost_type);
         a.t_hist = c->hist; a.t_target = c->target; a.t_forcing = c->forcing; a.t_yhist = c->yhist; a.t_scal = c->scal;
         if (c->front) { a.t_forcing = c->hforc; a.t_yhist = c->lam; a.t_ytarget = c->termU; }      // fused front: lambda_N itself, into lambda's history
         a.t_gpart = (c->gpart_on && c->gpart_terminal && c->have_guard) ? c->gpart : nullptr; a.t_gpart_n = c->gpart_n;

@@ -281,7 +281,7 @@ struct TinyArgs {
     double *scal; int *status;
     double *mirror; unsigned long long mirror_seq;
     int Np, cp, N, c, n_ops, m, nt, n_ess, n_pcof;
-    int cost;                                   // 0 no target, 1 :Infidelity, 2 :Tracking, 3 :Norm
+    int cost;                                   // 0 no target, 1 :Infidelity, 2 :Tracking, 3 :Norm, 4 :StateTransfer
     int gradient;                               // 0: forward evaluation only (scalars)
     int B, blen;                                // blocks of the scan
     double dt, tf;
@@ -571,13 +571,23 @@ __global__ __launch_bounds__(512) void k_tiny_scan(const TinyArgs a)
             const int col = tid >> 2, r = tid & 3;
             if (col < c && r < N && a.cost) {
                 const double u = PSI[S * 32 + col * 8 + 2 * r], v = PSI[S * 32 + col * 8 + 2 * r + 1], tr = TGT[col * 8 + 2 * r], ti = TGT[col * 8 + 2 * r + 1];
-                if (a.cost == 1) { av = u * tr + v * ti; bv = u * ti - v * tr; }      // <w_N, R>; <w_N, T>, T = [R_im; -R_re]
+                if (a.cost == 1 || a.cost == 4) { av = u * tr + v * ti; bv = u * ti - v * tr; }      // <w_N, R>; <w_N, T>, T = [R_im; -R_re]
                 else { const double du = u - (a.cost == 2 ? tr : 0.0), dv = v - (a.cost == 2 ? ti : 0.0); av = 0.5 * (du * du + dv * dv); }
             }
         }
         if (tid < 64) {
-            for (int off = 8; off > 0; off >>= 1) { av += __shfl_down(av, off); bv += __shfl_down(bv, off); }
-            if (tid == 0) { RED[32] = av; RED[33] = bv; }
+            if (a.cost == 4) {
+                // :StateTransfer: the four lanes of a column are added (lane 4 col then holds a_col, b_col, kept in RED[40 + 2 col]
+                // for y_N), then the squares a_j^2 + b_j^2 of the four columns by the rest of the tree: J = 1 - sum / c
+                for (int off = 2; off > 0; off >>= 1) { av += __shfl_down(av, off); bv += __shfl_down(bv, off); }
+                if (tid < 16 && (tid & 3) == 0) { RED[40 + 2 * (tid >> 2)] = av; RED[41 + 2 * (tid >> 2)] = bv; }
+                av = (tid < 16 && (tid & 3) == 0) ? av * av + bv * bv : 0.0; bv = 0.0;
+                for (int off = 8; off > 2; off >>= 1) av += __shfl_down(av, off);
+                if (tid == 0) { RED[32] = 1.0 - av / (double)c; RED[33] = 0.0; }
+            } else {
+                for (int off = 8; off > 0; off >>= 1) { av += __shfl_down(av, off); bv += __shfl_down(bv, off); }
+                if (tid == 0) { RED[32] = av; RED[33] = bv; }
+            }
         }
     }
     __syncthreads();
@@ -600,7 +610,9 @@ __global__ __launch_bounds__(512) void k_tiny_scan(const TinyArgs a)
     }
     if (tid < 4) {                                      // y_N for column tid -> Y[S] and the top block end
         const int col = tid;
-        const double av = RED[32], bv = RED[33], sc = 2.0 / ((double)a.n_ess * (double)a.n_ess);
+        const bool st = a.cost == 4;      // :StateTransfer: the column's own overlaps and 2/c
+        const double av = st ? RED[40 + 2 * col] : RED[32], bv = st ? RED[41 + 2 * col] : RED[33];
+        const double sc = st ? 2.0 / (double)c : 2.0 / ((double)a.n_ess * (double)a.n_ess);
         cx y[4];
         #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -608,7 +620,7 @@ __global__ __launch_bounds__(512) void k_tiny_scan(const TinyArgs a)
             const double tr = TGT[col * 8 + 2 * r], ti = TGT[col * 8 + 2 * r + 1];
             const double fu = F[S * 32 + col * 8 + 2 * r], fv = F[S * 32 + col * 8 + 2 * r + 1];
             double yu, yv;
-            if (a.cost == 1) { yu = sc * (av * tr + bv * ti) + fu; yv = sc * (av * ti - bv * tr) + fv; }
+            if (a.cost == 1 || st) { yu = sc * (av * tr + bv * ti) + fu; yv = sc * (av * ti - bv * tr) + fv; }
             else if (a.cost == 2) { yu = (tr - PSI[S * 32 + col * 8 + 2 * r]) + fu; yv = (ti - PSI[S * 32 + col * 8 + 2 * r + 1]) + fv; }
             else { yu = -PSI[S * 32 + col * 8 + 2 * r] + fu; yv = -PSI[S * 32 + col * 8 + 2 * r + 1] + fv; }
             y[r] = on ? (cx){yu, yv} : (cx){0.0, 0.0};

@@ -67,6 +67,11 @@ class RcclEvaluation:
     def eval_forward(self, pcof, uv_history=None):
         return self.dp.eval_forward(pcof, uv_history)
 
+    def set_cost_type(self, cost_type="Infidelity"):
+        """As DeviceProblem.set_cost_type, on every rank alike.  ``StateTransfer`` runs on time shards; with column shards
+        the evaluations refuse it (QGD_ERR_UNSUPPORTED, before any collective): a rank does not know the global column count."""
+        self.dp.set_cost_type(cost_type)
+
     def timings(self):
         return self.dp.timings()
 
@@ -145,6 +150,10 @@ class DeviceBackend:
     def set_timing(self, mode, phase=None):
         self.dp.set_timing(mode, phase)
 
+    def set_cost_type(self, cost_type="Infidelity"):
+        """As DeviceProblem.set_cost_type (every rank alike; the terminal stage runs on the rank that owns the final time)."""
+        self.dp.set_cost_type(cost_type)
+
     def close(self):
         self.dp.close()
 
@@ -182,10 +191,12 @@ class ColumnBackend:
         _lib.check(self.h, self.lib.qgd_cols_adjoint(self.h, 1 if self.rank == 0 else 0))
 
     finish, timings, set_timing, close = DeviceBackend.finish, DeviceBackend.timings, DeviceBackend.set_timing, DeviceBackend.close
+    set_cost_type = DeviceBackend.set_cost_type      # (``StateTransfer``: forward() and adjoint() refuse it, QGD_ERR_UNSUPPORTED)
 
 
 class ColumnSharded:
-    """discrete_adjoint! with the columns spread over the ranks: two small all-reduces per evaluation."""
+    """discrete_adjoint! with the columns spread over the ranks: two small all-reduces per evaluation.  Cost type
+    ``StateTransfer`` is refused: the backend's forward() raises (QGD_ERR_UNSUPPORTED) before the first all-reduce."""
 
     def __init__(self, backend, comm):
         self.b, self.comm = backend, comm

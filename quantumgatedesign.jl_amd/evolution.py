@@ -104,13 +104,14 @@ def finite_difference_quotient(costs, dpcof):
 
 def objective_from_scalars(scalars, N_ess, plain):
     """The objective of every row of ``scalars [K, 3]`` (the three scalars of eval_forward): infidelity (``plain``) or the
-    tracking / norm cost, plus the guard penalty -- the expression of eval_grad_finite_difference's cost."""
+    tracking / norm / state-transfer cost, plus the guard penalty -- the expression of eval_grad_finite_difference's cost."""
     sc = np.asarray(scalars, dtype=np.float64).reshape(-1, 3)
-    a, b, guard = sc[:, 0], sc[:, 1], sc[:, 2]      # (:Tracking / :Norm: a is the cost itself, b = 0)
+    a, b, guard = sc[:, 0], sc[:, 1], sc[:, 2]      # (:Tracking / :Norm / :StateTransfer: a is the cost itself, b = 0)
     return (1.0 - (a * a + b * b) / N_ess ** 2 if plain else a) + guard
 
 
-COST_TYPES = {"Infidelity": 0, ":Infidelity": 0, "Tracking": 1, ":Tracking": 1, "Norm": 2, ":Norm": 2}
+COST_TYPES = {"Infidelity": 0, ":Infidelity": 0, "Tracking": 1, ":Tracking": 1, "Norm": 2, ":Norm": 2,
+              "StateTransfer": 3, ":StateTransfer": 3}
 
 
 class DeviceProblem:
@@ -573,14 +574,25 @@ class DeviceProblem:
 
     def set_cost_type(self, cost_type="Infidelity"):
         """cost_type of discrete_adjoint / eval_grad_forced (eval_grad_discrete_adjoint.jl:26-35): ``Infidelity``,
-        ``Tracking`` (0.5 |w_N - target|^2) or ``Norm`` (0.5 |w_N|^2); a leading ':' as in Julia is accepted.
-        Anything else raises like the reference ("Invalid cost type")."""
+        ``Tracking`` (0.5 |w_N - target|^2), ``Norm`` (0.5 |w_N|^2) or ``StateTransfer`` (the per-column infidelity
+        1 - mean_j |t_j^H psi_j|^2, ``state_transfer_infidelity``: every column may arrive with a phase of its own); a
+        leading ':' as in Julia is accepted.  Anything else raises like the reference ("Invalid cost type")."""
         code = COST_TYPES.get(str(cost_type))
         if code is None:
             raise ValueError(f"Invalid cost type: {cost_type}")
         if code != getattr(self, "_cost_type", 0):
             _lib.check(self.h, self.lib.qgd_set_cost_type(self.h, code))
             self._cost_type = code
+
+    def column_overlaps(self):
+        """The overlaps ``o_j = t_j^H psi_j`` (complex, one per column) of the final state of the stored sweep with the
+        target, whatever the cost type (qgd_get_intermediate "column_overlaps")."""
+        ab = self.intermediate("column_overlaps")
+        return ab[:, 0] - 1j * ab[:, 1]
+
+    def column_fidelities(self):
+        """``|o_j|^2`` of every column: ``1 - mean(column_fidelities())`` is the ``StateTransfer`` cost."""
+        return np.abs(self.column_overlaps()) ** 2
 
     def set_small_path(self, on=True):
         """qgd_set_small_path: the four-launch evaluation of small problems (N <= 4: Rabi, cnot2) on / off for this handle."""
@@ -618,6 +630,8 @@ class DeviceProblem:
             return z[..., 0] + 1j * z[..., 1]
         if name == "repivoted":
             return int(out[0])
+        if name == "column_overlaps":
+            return out.reshape(self.c, 2)
         if name in ("selection", "small_path", "front_path", "batch_path"):
             return out
         if name == "sigma":
@@ -1244,6 +1258,23 @@ def infidelity_real(psi, target, N_ess):
     T = np.vstack([R[N:], -R[:N]])
     psi = np.asarray(psi, float)
     return 1 - (np.sum(psi * R) ** 2 + np.sum(psi * T) ** 2) / N_ess ** 2
+
+
+def state_transfer_infidelity(psi, target):
+    """The ``StateTransfer`` cost ``1 - (1/c) sum_j |t_j^H psi_j|^2`` (host arithmetic).  ``psi``: complex ``[N, c]``,
+    real ``[2N, c]``, or a real history whose last slot is taken (``[2N, slots, c]`` of eval_states, ``[2N, 1 + m, nt, c]``
+    of eval_forward).  ``target``: complex ``[N, c]`` or real ``[2N, c]``; its columns are expected to have unit norm."""
+    psi, target = np.asarray(psi), np.asarray(target)
+    if psi.ndim == 4:
+        psi = psi[:, 0, -1, :]
+    elif psi.ndim == 3:
+        psi = psi[:, -1, :]
+    R = target.astype(np.float64) if not np.iscomplexobj(target) else complex_to_real(target)
+    w = psi.astype(np.float64) if not np.iscomplexobj(psi) else complex_to_real(psi)
+    N = R.shape[0] // 2
+    T = np.vstack([R[N:], -R[:N]])
+    a, b = np.sum(w * R, axis=0), np.sum(w * T, axis=0)
+    return 1.0 - np.sum(a * a + b * b) / R.shape[1]
 
 
 def infidelity(*args, order=2):

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import jld2io
 from .controls import get_number_of_control_parameters
-from .evolution import device_problem
+from .evolution import COST_TYPES, device_problem
 
 
 @dataclass
@@ -89,10 +89,20 @@ class _Stop(Exception):
 
 
 def optimize_gate(schro_prob, controls, pcof_init, target, order=4, pcof_L=None, pcof_U=None, maxIter=50,
-                  print_level=5, ridge_penalty_strength=1e-2, max_cpu_time=60.0 * 60 * 24, filename=None):
+                  print_level=5, ridge_penalty_strength=1e-2, max_cpu_time=60.0 * 60 * 24, filename=None,
+                  cost_type="Infidelity"):
     """optimize_gate(prob, controls, pcof_init, target; order=4, pcof_L, pcof_U, maxIter=50,
-    print_level=5, ridge_penalty_strength=1e-2, max_cpu_time) -> OptimizationHistory."""
+    print_level=5, ridge_penalty_strength=1e-2, max_cpu_time) -> OptimizationHistory.
+
+    ``cost_type`` (not in the reference's optimize_gate): what the final state is measured by, one of ``COST_TYPES``.
+    With a type other than ``Infidelity`` the objective is cost + guard penalty + ridge penalty with the cost the
+    device returns (``StateTransfer``: the per-column infidelity), the history's ``infidelity`` column holds that cost,
+    and the result file's ``Setup`` group names the type."""
     from scipy.optimize import minimize
+
+    if COST_TYPES.get(str(cost_type)) is None:
+        raise ValueError(f"Invalid cost type: {cost_type}")
+    plain = COST_TYPES[str(cost_type)] == 0
 
     pcof_init = np.asarray(pcof_init, dtype=np.float64)
     N_coeff = get_number_of_control_parameters(controls)
@@ -118,10 +128,15 @@ def optimize_gate(schro_prob, controls, pcof_init, target, order=4, pcof_L=None,
         setup["pcof_L"] = np.broadcast_to(np.asarray(pcof_L, float), (N_coeff,)).copy()
     if pcof_U is not None:
         setup["pcof_U"] = np.broadcast_to(np.asarray(pcof_U, float), (N_coeff,)).copy()
+    if not plain:      # (only then: files of the default type stay as they were)
+        setup["cost_type"] = str(cost_type).lstrip(":")
 
     def fun(pcof):
         grad, out3 = dp.discrete_adjoint(pcof)                                       # :257-268, :304
-        infid = 1.0 - (out3[0] ** 2 + out3[1] ** 2) / schro_prob.N_ess_levels ** 2   # infidelity.jl:17
+        if plain:
+            infid = 1.0 - (out3[0] ** 2 + out3[1] ** 2) / schro_prob.N_ess_levels ** 2   # infidelity.jl:17
+        else:
+            infid = float(out3[0])                                                   # { cost, 0, guard penalty }
         ridge = float(pcof @ pcof) * ridge_penalty_strength / len(pcof)              # :272
         grad = grad + 2.0 * ridge_penalty_strength * pcof / len(pcof)                # :311
         obj = infid + out3[2] + ridge
@@ -151,13 +166,17 @@ def optimize_gate(schro_prob, controls, pcof_init, target, order=4, pcof_L=None,
 
     bounds = list(zip(bound(pcof_L, -np.inf), bound(pcof_U, np.inf)))                # :385-403
     res = None
+    dp.set_cost_type(cost_type)
     try:
-        res = minimize(fun, pcof_init, jac=True, method="L-BFGS-B", bounds=bounds, callback=callback,
-                       options=dict(maxiter=maxIter, maxcor=40, ftol=1e-15, gtol=1e-9, maxls=30))
-    except _Stop:
-        pass
-    if res is not None and not np.array_equal(res.x, last["pcof"]):
-        fun(np.asarray(res.x, dtype=np.float64))       # make `last` describe the returned iterate
+        try:
+            res = minimize(fun, pcof_init, jac=True, method="L-BFGS-B", bounds=bounds, callback=callback,
+                           options=dict(maxiter=maxIter, maxcor=40, ftol=1e-15, gtol=1e-9, maxls=30))
+        except _Stop:
+            pass
+        if res is not None and not np.array_equal(res.x, last["pcof"]):
+            fun(np.asarray(res.x, dtype=np.float64))       # make `last` describe the returned iterate
+    finally:
+        dp.set_cost_type("Infidelity")
     if not len(hist) or not np.array_equal(hist.pcof[-1], last["pcof"]):
         hist.iter_count.append(len(hist.iter_count)); hist.ipopt_obj_value.append(last["obj"])
         hist.wall_time.append(time.time() - t0); hist.pcof.append(last["pcof"])
