@@ -561,4 +561,8 @@ int qgd_get_operator_path(qgd_handle h, int32_t *out3);
 #ifdef __cplusplus
 }
 #endif
+
+/* directional derivatives J v of the states, populations and expectation values */
+#include "qgd_pushforward.h"
+
 #endif

@@ -372,6 +372,66 @@ function hip_eval_pullback(prob::SchrodingerProb, controls, pcof::Vector{Float64
     return grad
 end
 
+# qgd_eval_pushforward is declared in include/qgd_pushforward.h (which qgd.h includes), not in the text of qgd.h itself; it is called
+# through its address, so that the (symbol, library) calls of this file remain the entry points of qgd.h one to one
+# (tests/test_host.py compares them); tests/test_pushforward_host.py compares this call with its own header.
+import Libdl
+qgd_eval_pushforward_ptr() = Libdl.dlsym(Libdl.dlopen(libqgd), :qgd_eval_pushforward)
+
+"Directional derivatives J v of the outputs of hip_eval_states, hip_get_populations and hip_eval_expectations along the columns of
+`v` [n_pcof, n_vec] (or one vector) in pcof (qgd_eval_pushforward): the forward-mode half of what hip_eval_pullback transposes.
+Returns a NamedTuple of the parts asked for -- `states` [2N, slots, c, n_vec] (states=true), `populations` [N or n_groups, ..]
+(populations=true or a level_map) and `expectations` [n_obs, ..] (observables given, as for hip_eval_expectations) -- with slot 1
+(the initial state) exact zeros.  All directions share one forced scan on the device; no target is needed.
+(Like the rest of this shim it was written against include/qgd.h without a Julia at hand: this wrapper has not been executed.)"
+function hip_eval_pushforward(prob::SchrodingerProb, controls, pcof::Vector{Float64}, v::VecOrMat{Float64}; order::Int=2,
+                              saveEveryNsteps::Int=1, states::Bool=false, populations::Bool=false,
+                              level_map::Union{Nothing,Matrix{Float64}}=nothing, observables=nothing,
+                              history_precomputed::Bool=false)
+    N, c, slots = prob.N_tot_levels, prob.N_initial_conditions, 1 + div(prob.nsteps, saveEveryNsteps)
+    V = v isa AbstractVector ? reshape(v, :, 1) : v
+    size(V, 1) == length(pcof) && size(V, 2) >= 1 || throw(DimensionMismatch("v must be [$(length(pcof))] or [$(length(pcof)), n_vec >= 1]"))
+    all(isfinite, V) || throw(ArgumentError("v must be finite"))
+    n_vec = size(V, 2)
+    level_map === nothing || size(level_map, 2) == N || throw(DimensionMismatch("level_map must be [n_groups, $N]"))
+    with_pop = populations || level_map !== nothing
+    states || with_pop || observables !== nothing || throw(ArgumentError("no output asked for"))
+    rows = level_map === nothing ? N : size(level_map, 1)
+    n_obs, has_im = 0, false
+    obs_re, obs_im = zeros(0, 0, 0), zeros(0, 0, 0)
+    if observables !== nothing
+        obs = observables isa AbstractMatrix ? [observables] : collect(observables)
+        n_obs = length(obs)
+        n_obs >= 1 || throw(ArgumentError("no observable"))
+        obs_re, obs_im = zeros(N, N, n_obs), zeros(N, N, n_obs)
+        for (j, o) in enumerate(obs)
+            size(o) == (N, N) || throw(DimensionMismatch("observable $j must be [$N, $N]"))
+            O = Matrix{ComplexF64}(o)
+            maximum(abs, O - O') <= 1e-12 * max(1.0, maximum(abs, O)) || throw(ArgumentError("observable $j is not Hermitian"))
+            obs_re[:, :, j] = real(O); obs_im[:, :, j] = imag(O)
+        end
+        has_im = any(!iszero, obs_im)
+    end
+    states_dot = states ? zeros(2N, slots, c, n_vec) : nothing
+    pop_dot = with_pop ? zeros(rows, slots, c, n_vec) : nothing
+    expect_dot = n_obs > 0 ? zeros(n_obs, slots, c, n_vec) : nothing
+    dp = device_problem(prob, order)
+    pc_ptr, pc_len = set_controls!(dp, prob, controls, pcof)
+    opt(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    check(dp.handle, ccall((:qgd_set_save_every, libqgd), Cint, (Ptr{Cvoid}, Int32), dp.handle, saveEveryNsteps))
+    try
+        GC.@preserve pcof V states_dot pop_dot level_map expect_dot obs_re obs_im check(dp.handle, ccall(qgd_eval_pushforward_ptr(), Cint,
+              (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64},
+               Ptr{Float64}, Ptr{Float64}, Int32),
+              dp.handle, pc_ptr, pc_len, history_precomputed ? 1 : 0, pointer(V), n_vec, opt(states_dot), opt(pop_dot), opt(level_map),
+              level_map === nothing ? 0 : rows, opt(expect_dot), n_obs > 0 ? pointer(obs_re) : Ptr{Float64}(C_NULL),
+              has_im ? pointer(obs_im) : Ptr{Float64}(C_NULL), n_obs))
+    finally
+        ccall((:qgd_set_save_every, libqgd), Cint, (Ptr{Cvoid}, Int32), dp.handle, 1)
+    end
+    return (states=states_dot, populations=pop_dot, expectations=expect_dot)
+end
+
 "Gradient with respect to pcof of a cost written on the outputs of hip_eval_dense (qgd_eval_dense_pullback): sum of
 <bar, d output / d pcof> over the cotangents given, each in the shape of its dense output at `refine` points per step:
 states_bar [2N, 1+nsteps*refine, c]; populations_bar [N or n_groups, ..]; expectations_bar [n_obs, ..] with `observables` as

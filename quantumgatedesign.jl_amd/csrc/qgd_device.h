@@ -221,6 +221,8 @@ int qgdk_hess_wapply(const qgdk_ctx *c, const double *shist, double *ws, int n_d
 size_t qgdk_hvp_gv_len(const qgdk_ctx *c);
 int qgdk_hvp_gv(const qgdk_ctx *c, const double *v, double *gvt);
 int qgdk_hvp_forced_sweep(const qgdk_ctx *c, const double *gvt, const void *one3, double *phi, double *bnd, double *sv);
+int qgdk_hvp_gv_dirs(const qgdk_ctx *c, const double *v, double *gvt, int n_dir);
+int qgdk_hvp_forced_sweep_dirs(const qgdk_ctx *c, const double *gvt, const void *basis, double *phi, double *bnd, double *sv, int n_dir);
 int qgdk_hvp_forcing(const qgdk_ctx *c, const double *Z, const double *half, const double *sv, const double *ws,
                      const double *gvt, const double *term, double *F, double *part);
 int qgdk_hvp_adjoint(const qgdk_ctx *a);
@@ -230,6 +232,13 @@ int qgdk_hvp_contract(const qgdk_ctx *c, const double *part, const double *gB, d
    sbar, pbar, ebar may be null); every panel is written */
 int qgdk_pullback_forcing(const qgdk_ctx *c, double *F, int save, const double *sbar, const double *pbar, const double *map_dev,
                           int n_groups, const double *ebar, const double *obs_re, const double *obs_im, int n_obs);
+/* qgd_k_pushforward.hip: tangents of the level populations and the expectation values along n_dir directions.  State panels
+   c->hist and tangent panels sv [nt][Np][2 n_dir cp] (direction j in the columns j cp ..) -> pop [N or n_groups, n_slots, c, n_dir]
+   and expect [n_obs, n_slots, c, n_dir] (device, column-major; each may be null), slot k at time point k * save, slot 0 zeros:
+   2 (u du + v dv), contracted with map_dev [n_groups x N] when given, and 2 Re(psi^H H_j dpsi) with H_j the Hermitian part of
+   obs_re + i obs_im ([N x N x n_obs] column-major; obs_im null: real observables).  Fixed order of every sum */
+int qgdk_pushforward_outputs(const qgdk_ctx *c, const double *sv, int n_dir, int save, double *pop, const double *map_dev, int n_groups,
+                             double *expect, const double *obs_re, const double *obs_im, int n_obs);
 int qgdk_forcing_terms(const qgdk_ctx *c);
 int qgdk_forcing_add_derivs(const qgdk_ctx *c);
 int qgdk_forcing_sweep(const qgdk_ctx *c);

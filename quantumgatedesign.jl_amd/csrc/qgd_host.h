@@ -1,8 +1,9 @@
-// qgd_host.h -- what the six host-side translation units of the C ABI share (include/qgd.h): the handle, the error and
+// qgd_host.h -- what the seven host-side translation units of the C ABI share (include/qgd.h): the handle, the error and
 // launch macros, the phase timer and the internal entry points of each unit.
 //   qgd_host_alloc.cpp    handles: creation, validation (SchrodingerProb.jl:73-154), the time grid and its windows, setters
 //   qgd_host_eval.cpp     one evaluation: forward / adjoint phases, result transport, the evaluation entry points
 //   qgd_host_sens.cpp     sensitivities of the state to the parameters: the forced gradient, the exact Hessian, Hessian-vector products, pullbacks (grid points and dense output)
+//   qgd_host_pushforward.cpp  directional derivatives of the trajectory outputs (include/qgd_pushforward.h)
 //   qgd_host_output.cpp   reference-layout output arrays of a resident or windowed grid: the copy stream, staging, the one transport
 //   qgd_host_windows.cpp  time grids in bounded memory: window entry, the windowed forward and adjoint passes
 //   qgd_host_comm.cpp     several GPUs: the RCCL binding, the collective evaluation and its failure mode
@@ -58,6 +59,9 @@ using qgdh::Phase;
 //   SWEEP_FRONT only, whose k_psi formed L_N^-H times the terminal value of the old ones (the general path re-forms the
 //   terminal condition on reuse); kind and pcof stay, so the sweep can still be redone.
 // derivs: the stage derivatives of the stored history are in place.  Every transition that replaces the history clears it.
+// forced_basis: the forced basis responses of the stored history (k.fs_BR, k.fs_BL in POOL_FORCED) are in place, as long as that
+//   pool still stands under its key (forced_missing(h) == 0); cleared with derivs.  qgd_eval_pushforward skips qgdk_forced_basis
+//   on it; the other entry points that form the responses record it and form them on every call, as before.
 // front: what qgd_get_intermediate("front_path") reports -- whether the last forward evaluation took the fused front.  A setter
 //   that voids the sweep leaves it (and the same-point matrices in the buffers).
 // New control tables void the sweep on a windowed grid only: there a reused sweep re-runs its windows from the caller's tables;
@@ -73,6 +77,7 @@ struct StoredSweep {
     bool gradient = false;
     bool reusable = false;
     bool derivs = false;
+    bool forced_basis = false;
     bool front = false;
 };
 
@@ -83,6 +88,8 @@ struct StoredSweep {
 // pool_release frees them, writes NULL (and length 0) into every slot and clears the key; pool_missing: the bytes pool_ensure
 // would allocate for a (key, plan) pair.  The other functions are in qgd_host_alloc.cpp.
 #define QGD_BATCH_CHUNK_MAX 1024      // members of a batch that share one set of launches (qgd_eval_batch)
+#define QGD_PUSHFORWARD_CHUNK_MAX 4096     // directions of a pushforward that ride along in one forced scan (qgd_eval_pushforward) ...
+#define QGD_PUSHFORWARD_CHUNK_DEFAULT 256  // ... and without QGD_PUSHFORWARD_CHUNK (cnot3's 180 in one scan: 812 MB of tangent history; 13.2 ms against 16.8 in chunks of 32)
 struct Buf { double **slot; size_t count; bool on = true; };
 inline size_t plan_bytes(const std::vector<Buf> &plan) { size_t n = 0; for (const Buf &b : plan) n += b.on ? b.count : 0; return n * sizeof(double); }
 struct Grown { double *p = nullptr; size_t len = 0; };
@@ -93,7 +100,7 @@ struct Pool {
 };
 struct KeyedPlan { std::vector<size_t> key; std::vector<Buf> plan; };
 inline size_t pool_missing(const Pool &pool, const KeyedPlan &p) { return pool.key == p.key ? 0 : plan_bytes(p.plan); }
-enum { POOL_FORCED, POOL_HESS, POOL_HVP, POOL_PULLBACK, POOL_DENSE, POOL_BATCH, POOL_DENSE_PULLBACK, N_SENS_POOLS, POOL_FORCING = N_SENS_POOLS, POOL_STAGE, N_POOLS };
+enum { POOL_FORCED, POOL_HESS, POOL_HVP, POOL_PULLBACK, POOL_DENSE, POOL_BATCH, POOL_DENSE_PULLBACK, POOL_PUSHFORWARD, N_SENS_POOLS, POOL_FORCING = N_SENS_POOLS, POOL_STAGE, N_POOLS };
 
 struct qgd_handle_s {
     qgdk_ctx k{};
@@ -114,6 +121,7 @@ struct qgd_handle_s {
     //   POOL_DENSE     qgd_eval_dense (dense_panels, dense_w); key (time points, refine, panel size, m, bits of dt)
     //   POOL_BATCH     qgd_eval_batch on the small-problem path (bt): the arrays of a chunk's members; key (chunk members, nt, m, n_ops, n_pcof)
     //   POOL_DENSE_PULLBACK  qgd_eval_dense_pullback (dpb); key (time points, refine, n_pcof, m, bits of dt, the lengths of the five uploads)
+    //   POOL_PUSHFORWARD  qgd_eval_pushforward (pf); key (nt, n_pcof, basis directions, scan blocks, directions of a chunk, the lengths of the three staged outputs and the two uploads)
     //   POOL_FORCING   qgd_eval_forward with a user forcing (k.ff_*, fsc_forcing); key (nt, scan blocks)
     //   POOL_STAGE     the staging buffers of the reference-layout outputs: no key, each made or grown on first need
     Pool pools[N_POOLS];
@@ -149,6 +157,18 @@ struct qgd_handle_s {
         double *G = nullptr, *gbar = nullptr, *F = nullptr, *Y = nullptr, *mu = nullptr, *sigma = nullptr, *cpart = nullptr, *gB = nullptr, *scal = nullptr;
         double *sbar = nullptr, *pbar = nullptr, *map = nullptr, *ebar = nullptr, *planes = nullptr;
     } dpb;
+    // qgd_eval_pushforward: the tangent history sv of the directions of one chunk side by side, the scan
+    // buffers and the direction table of that width, the one-operator bases {0 | w, 0} of every width w up to the chunk's, the
+    // chunk's directions, the staged outputs and the caller's level map and observable planes on the device -- nothing shared
+    // with the Hessian-vector setup, which a pushforward of the same sweep leaves valid.  width: the directions sv[0] and bnd[0]
+    // were last zeroed for.  The largest chunk: QGD_PUSHFORWARD_CHUNK, read when the handle is created (the tests force small
+    // chunks with it), and what fits the memory budget
+    struct PushforwardBufs {
+        double *sv = nullptr, *phi = nullptr, *bnd = nullptr, *gvt = nullptr, *bases = nullptr, *v = nullptr;
+        double *st = nullptr, *po = nullptr, *ex = nullptr, *map = nullptr, *planes = nullptr;
+        size_t width = 0;
+    } pf;
+    int pf_chunk_max = (getenv("QGD_PUSHFORWARD_CHUNK") && atoi(getenv("QGD_PUSHFORWARD_CHUNK")) >= 1) ? std::min(atoi(getenv("QGD_PUSHFORWARD_CHUNK")), QGD_PUSHFORWARD_CHUNK_MAX) : QGD_PUSHFORWARD_CHUNK_DEFAULT;
     // qgd_eval_batch: per member of a chunk the small-problem path's compact arrays, its scalars and
     // status word, its coefficients and its result row; the pinned staging buffer [pcofs | rows] of one chunk; the largest chunk
     // (QGD_BATCH_CHUNK, read when the handle is created: the tests force small chunks with it); the route of the last batch
@@ -337,7 +357,7 @@ struct PhaseTimer {
 
 // The transitions of the StoredSweep record (described at its declaration).
 inline void hvp_void(qgd_handle h) { h->hvp_valid = false; }
-inline void sweep_void(qgd_handle h) { h->sweep.kind = SWEEP_NONE; h->sweep.derivs = false; hvp_void(h); }
+inline void sweep_void(qgd_handle h) { h->sweep.kind = SWEEP_NONE; h->sweep.derivs = false; h->sweep.forced_basis = false; hvp_void(h); }
 
 // a forward sweep is about to overwrite the buffers (after the checks that can refuse the call, before the first launch)
 inline void sweep_begin(qgd_handle h) { sweep_void(h); h->sweep.front = false; }
@@ -352,6 +372,7 @@ inline void sweep_done(qgd_handle h, SweepKind kind, const double *pcof, int n_p
     s.gradient = gradient;
     s.reusable = true;
     s.derivs = false;
+    s.forced_basis = false;
     s.front = kind == SWEEP_FRONT;
 }
 
@@ -450,6 +471,10 @@ void free_sensitivity_buffers(qgd_handle h);
 void drop_graph(qgd_handle h);
 int plan_windows(qgd_handle h, int chunks, int win);
 int alloc_grid(qgd_handle h);
+
+// qgd_host_sens.cpp
+int forced_buffers(qgd_handle h, size_t nt, size_t B);
+size_t forced_missing(qgd_handle h);
 
 // qgd_host_output.cpp
 qgd_handle_s::HostReg *find_reg(qgd_handle h, const void *p, size_t bytes);

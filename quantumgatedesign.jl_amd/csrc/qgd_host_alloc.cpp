@@ -64,7 +64,7 @@ int pool_ensure(qgd_handle h, Pool &pool, const KeyedPlan &p, const char *fit, s
 }
 
 
-// the sensitivity pools (forced gradient, Hessian, Hessian-vector product, pullback, dense output, batch, dense pullback) follow the grid and the control basis
+// the sensitivity pools (forced gradient, Hessian, Hessian-vector product, pullback, dense output, batch, dense pullback, pushforward) follow the grid and the control basis
 void free_sensitivity_buffers(qgd_handle h)
 {
     for (int i = 0; i < N_SENS_POOLS; i++) pool_release(h->pools[i]);

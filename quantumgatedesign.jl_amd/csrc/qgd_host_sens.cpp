@@ -20,16 +20,20 @@ static KeyedPlan forced_plan(qgd_handle h, size_t nt, size_t B)
         {&h->fsc_forced, nt * (size_t)(k.cp / 8) * (size_t)(2 * k.m + 2) * k.Np * 16, qgdk_forced_lds(k.Np, k.m) > 150 * 1024}}};
 }
 
-static int forced_buffers(qgd_handle h, size_t nt, size_t B)
+namespace qgdh {
+
+int forced_buffers(qgd_handle h, size_t nt, size_t B)
 {
     const int rc = pool_ensure(h, h->pools[POOL_FORCED], forced_plan(h, nt, B));
     if (!rc) h->k.fs_scratch = h->fsc_forced;
     return rc;
 }
 
-// QGD_ERR_MEMORY of a second-order entry point is decided from what ITS call allocates: its own plan and, when they are not there
-// under the right key, the forced gradient's buffers -- these bytes
-static size_t forced_missing(qgd_handle h) { return pool_missing(h->pools[POOL_FORCED], forced_plan(h, (size_t)h->k.nt, (size_t)h->k.scan_blocks)); }
+// QGD_ERR_MEMORY of a second-order entry point (and of qgd_eval_pushforward) is decided from what ITS call allocates: its own plan
+// and, when they are not there under the right key, the forced gradient's buffers -- these bytes
+size_t forced_missing(qgd_handle h) { return pool_missing(h->pools[POOL_FORCED], forced_plan(h, (size_t)h->k.nt, (size_t)h->k.scan_blocks)); }
+
+}  // namespace qgdh
 
 
 // what both second-order entry points refuse once they have entered (`name`: the entry point, `what`: its result, for the messages)
@@ -60,6 +64,7 @@ static int second_order_setup(qgd_handle h, const double *pcof, int n_pcof)
     if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
     if ((rc = forced_buffers(h, (size_t)k.nt, (size_t)k.scan_blocks))) return rc;
     { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); }
+    h->sweep.forced_basis = true;
     return QGD_OK;
 }
 
@@ -370,6 +375,7 @@ int qgd_eval_grad_forced(qgd_handle h, const double *pcof, int32_t n_pcof, doubl
         }
         if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = W == 1; }
         { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); }
+        h->sweep.forced_basis = W == 1;
         { PhaseTimer t(h, "forced_sweeps"); K_TRY(h, qgdk_forced_chains(&k)); }
         if (r + 1 < W)      // s at the start of the next window
             HIP_TRY(h, hipMemcpyAsync(k.fs_bnd, k.fs_bnd + (size_t)k.scan_blocks * hstepS, hstepS * sizeof(double), hipMemcpyDeviceToDevice, k.stream));

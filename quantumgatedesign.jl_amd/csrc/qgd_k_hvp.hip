@@ -32,6 +32,22 @@ __global__ __launch_bounds__(64) void k_hvp_gv(const double *__restrict__ G, con
     gvt[hv_gvi(n, b, NB / 2, nt)] = acc;
 }
 
+// The same for n_dir directions at once (qgd_eval_pushforward): one workgroup = (time point, direction j), v [n_pcof x n_dir]
+// column-major.  The table gets n_dir coefficient columns, gvt[((tau' nt + n)(M + 1) + d') n_dir + j]: a one-operator basis with
+// n_dir coefficients, whose "parameters" are the directions.  Each entry is the sum k_hvp_gv forms, in its order.
+__global__ __launch_bounds__(64) void k_hvp_gv_dirs(const double *__restrict__ G, const int64_t *__restrict__ goff, const int32_t *__restrict__ ncoef,
+                                                    const int32_t *__restrict__ poff, const double *__restrict__ v, double *__restrict__ gvt,
+                                                    int m, int NB, int nt, int gnt, int gn0, int n_pcof, int n_dir)
+{
+    const int n = blockIdx.x, j = blockIdx.y, b = threadIdx.x;
+    if (b >= NB) return;
+    const int o = b / (2 * m), tau = (b / m) % 2, d = b % m, nc = ncoef[o];
+    const double *g = G + goff[o] + (((size_t)tau * gnt + n + gn0) * (m + 1) + d) * nc, *vo = v + (size_t)j * n_pcof + poff[o];
+    double acc = 0.0;
+    for (int l = 0; l < nc; l++) acc += g[l] * vo[l];
+    gvt[hv_gvi(n, b, NB / 2, nt) * n_dir + j] = acc;
+}
+
 // One workgroup = (column group, time point); Np <= 64, NB <= 64.  One pass over the NB panels z_b(n) of the column group
 // (16-byte loads, a panel row of the group is 128 contiguous bytes) gives
 //   part[n][grp][b] = sum_{rows, columns of grp} s_v(n) . z_b(n) + sum_b' (half[b][b'] + half[b'][b]) gv[n][b']
@@ -155,12 +171,30 @@ int qgdk_hvp_gv(const qgdk_ctx *c, const double *v, double *gvt)
     return (int)hipGetLastError();
 }
 
+// the direction table of n_dir directions at once (v [n_pcof x n_dir] column-major on the device; gvt: n_dir * qgdk_hvp_gv_len doubles)
+int qgdk_hvp_gv_dirs(const qgdk_ctx *c, const double *v, double *gvt, int n_dir)
+{
+    const int NB = c->n_ops * 2 * c->m;
+    if (NB < 1 || NB > 64 || n_dir < 1 || n_dir > 65535) return -1;
+    hipLaunchKernelGGL(k_hvp_gv_dirs, dim3(c->nt, n_dir), dim3(64), 0, c->stream, c->G, c->goff, c->ncoef, c->poff, v, gvt, c->m, NB, c->nt,
+                       c->g_nt ? c->g_nt : c->nt, c->g_n0, c->n_pcof, n_dir);
+    return (int)hipGetLastError();
+}
+
 // s_v at every time point: the forced scan with the single direction gvt (sv [nt][Np][2cp], sv[0] zeroed by the caller;
 // phi [B][Np][2cp] and bnd [B+1][Np][2cp] scan buffers, bnd[0] zeroed by the caller; one3: device {goff = 0 | ncoef = 1, poff = 0})
 int qgdk_hvp_forced_sweep(const qgdk_ctx *c, const double *gvt, const void *one3, double *phi, double *bnd, double *sv)
 {
+    return qgdk_hvp_forced_sweep_dirs(c, gvt, one3, phi, bnd, sv, 1);
+}
+
+// the same with n_dir directions side by side, as column groups of one scan: the table of qgdk_hvp_gv_dirs, sv [nt][Np][2 n_dir cp]
+// with direction j in the columns j cp .. (the layout of qgd_eval_hessian's sensitivity history), phi and bnd n_dir times as wide,
+// basis: device {goff = 0 | ncoef = n_dir, poff = 0}
+int qgdk_hvp_forced_sweep_dirs(const qgdk_ctx *c, const double *gvt, const void *one3, double *phi, double *bnd, double *sv, int n_dir)
+{
     qgdk_ctx d = *c;
-    d.n_ops = 1; d.m = c->n_ops * c->m; d.n_pcof = 1;
+    d.n_ops = 1; d.m = c->n_ops * c->m; d.n_pcof = n_dir;
     d.G = const_cast<double *>(gvt);
     d.goff = (int64_t *)one3; d.ncoef = (int32_t *)((char *)one3 + 8); d.poff = (int32_t *)((char *)one3 + 12);
     d.g_nt = 0; d.g_n0 = 0;

@@ -466,6 +466,37 @@ class DeviceProblem:
                                                       0 if re is None else re.shape[2], _vp(grad)))
         return grad
 
+    def eval_pushforward(self, pcof, v, states=False, populations=False, level_map=None, observables=None,
+                         history_precomputed=False):
+        """Pushforward of directions in pcof to the trajectory outputs: ``J v`` with
+        ``J = d output / d pcof``, for ``v`` ``(n_pcof,)`` or ``(n_pcof, n_vec)`` (pushforward_directions).  Returns a dict of
+        the parts asked for: ``"states"`` (``states=True``, the shape of eval_states' result), ``"populations"``
+        (``populations=True``, or a ``level_map`` given: eval_populations' shape) and ``"expectations"`` (``observables`` given:
+        eval_expectations' shape), each Fortran-ordered with a trailing direction axis, which a 1-D ``v`` drops.  The forward
+        half of what eval_pullback transposes: ``<ybar, J v> = <eval_pullback(ybar), v>``.  All directions of a call share one
+        forced scan.  Honours set_save_every; slot 0 is exact zeros.  ``history_precomputed``: reuse the stored forward sweep
+        when it belongs to this pcof.  ``pcof=None``: tables and basis as they were set.  No target is needed."""
+        cols, single = pushforward_directions(v, self.n_pcof)
+        lm = None if level_map is None else level_map_array(level_map, self.N)
+        re, im = (None, None) if observables is None else observable_planes(observables, self.N)
+        if not (states or populations or lm is not None or re is not None):
+            raise ValueError("eval_pushforward needs at least one of states, populations (or level_map), observables")
+        tail = (self._slots(), self.c, cols.shape[1])
+        out = {}
+        if states:
+            out["states"] = np.zeros((2 * self.N,) + tail, order="F")
+        if populations or lm is not None:
+            out["populations"] = np.zeros((self.N if lm is None else lm.shape[0],) + tail, order="F")
+        if re is not None:
+            out["expectations"] = np.zeros((re.shape[2],) + tail, order="F")
+        pc, ptr, n = self._pcof_arg(pcof)
+        opt = lambda a: None if a is None else _vp(a)
+        _lib.check(self.h, self.lib.qgd_eval_pushforward(self.h, ptr, n, 1 if history_precomputed else 0, _vp(cols), cols.shape[1],
+                                                         opt(out.get("states")), opt(out.get("populations")), opt(lm),
+                                                         0 if lm is None else lm.shape[0], opt(out.get("expectations")), opt(re),
+                                                         opt(im), 0 if re is None else re.shape[2]))
+        return {key: (a[..., 0] if single else a) for key, a in out.items()}
+
     def eval_dense_pullback(self, refine, pcof=None, states_bar=None, populations_bar=None, level_map=None,
                             expectations_bar=None, observables=None, history_precomputed=False):
         """Pullback of the DENSE outputs to pcof: eval_pullback for a cost written on eval_dense_states,
@@ -1022,6 +1053,15 @@ def eval_dense(prob, controls, pcof, order=2, refine=2, output="states", level_m
     return dp.eval_dense_expectations(refine, observables, pcof)
 
 
+def level_map_array(level_map, N):
+    """A level map as the library takes it: Fortran-ordered float64 ``[n_groups >= 1, N]``; ValueError for anything else."""
+    lm = np.asarray(level_map)
+    if lm.ndim != 2 or lm.shape[1] != N or lm.shape[0] < 1 or lm.dtype == bool or not np.issubdtype(lm.dtype, np.number) \
+            or np.iscomplexobj(lm):
+        raise ValueError(f"level_map must be a real [n_groups >= 1, {N}] array; got {lm.dtype} {lm.shape}")
+    return np.asfortranarray(lm, dtype=np.float64)
+
+
 def pullback_cotangents(N, n_slots, n_cols, states_bar=None, populations_bar=None, level_map=None, expectations_bar=None,
                         observables=None):
     """The arguments of eval_pullback as the arrays the library takes, ``(states_bar, populations_bar, level_map,
@@ -1055,11 +1095,7 @@ def pullback_cotangents(N, n_slots, n_cols, states_bar=None, populations_bar=Non
     if level_map is not None:
         if populations_bar is None:
             raise ValueError("level_map given without populations_bar")
-        lm = np.asarray(level_map)
-        if lm.ndim != 2 or lm.shape[1] != N or lm.shape[0] < 1 or lm.dtype == bool or not np.issubdtype(lm.dtype, np.number) \
-                or np.iscomplexobj(lm):
-            raise ValueError(f"level_map must be a real [n_groups >= 1, {N}] array; got {lm.dtype} {lm.shape}")
-        lm = np.asfortranarray(lm, dtype=np.float64)
+        lm = level_map_array(level_map, N)
     if populations_bar is not None:
         pb = real(populations_bar, N if lm is None else lm.shape[0], "populations_bar")
     if (expectations_bar is None) != (observables is None):
@@ -1104,6 +1140,63 @@ def eval_dense_pullback(prob, controls, pcof, order=2, refine=2, states_bar=None
     dp = device_problem(prob, order)
     dp.set_controls(controls)
     return dp.eval_dense_pullback(refine, pcof, states_bar, populations_bar, level_map, expectations_bar, observables)
+
+
+def pushforward_directions(v, n_pcof):
+    """The directions of eval_pushforward as the library takes them: ``(cols, single)`` with ``cols`` a Fortran-ordered float64
+    ``[n_pcof, n_vec]`` and ``single`` whether ``v`` was one vector ``(n_pcof,)`` (the results then lose their direction axis).
+    ValueError for a wrong length or rank, complex or non-numeric input, an empty set of directions or non-finite values."""
+    a = np.asarray(v)
+    if a.dtype == bool or not np.issubdtype(a.dtype, np.number) or np.iscomplexobj(a):
+        raise ValueError(f"v must be a real numeric array; got dtype {a.dtype}")
+    if a.ndim not in (1, 2) or a.shape[0] != int(n_pcof):
+        raise ValueError(f"v must have shape ({int(n_pcof)},) or ({int(n_pcof)}, n_vec); got {a.shape}")
+    cols = np.asfortranarray(a.reshape(int(n_pcof), -1), dtype=np.float64)
+    if cols.shape[1] < 1 or cols.shape[0] < 1:
+        raise ValueError("v holds no direction")
+    if not np.all(np.isfinite(cols)):
+        raise ValueError("v must be finite")
+    return cols, a.ndim == 1
+
+
+def pushforward_outputs(N, output, level_map=None, observables=None):
+    """What ``output=`` of the functional eval_pushforward asks of DeviceProblem.eval_pushforward, as keyword arguments; the
+    refusals of eval_dense's ``output=`` argument, of level_map_array and of observable_planes."""
+    if output not in ("states", "populations", "expectations"):
+        raise ValueError("output must be 'states', 'populations' or 'expectations'")
+    if (output == "expectations") != (observables is not None):
+        raise ValueError("observables go with output='expectations'")
+    if level_map is not None and output != "populations":
+        raise ValueError("level_map goes with output='populations'")
+    if observables is not None:
+        observable_planes(observables, N)
+    if level_map is not None:
+        level_map_array(level_map, N)
+    return dict(states=output == "states", populations=output == "populations", level_map=level_map, observables=observables)
+
+
+def eval_pushforward(prob, controls, pcof, v, order=2, saveEveryNsteps=1, output="states", level_map=None, observables=None):
+    """Directional derivative ``J v`` of a trajectory output along ``v`` in pcof, ``J = d output / d pcof``: of the states
+    (``output="states"``, complex ``[N, slots, N_initial_conditions]`` as real_to_complex makes of the stacked tangent), of the
+    populations (``"populations"``, real ``[N, ..]`` or ``[n_groups, ..]`` with ``level_map``) or of the expectation values of
+    ``observables`` (``"expectations"``, real ``[n_obs, ..]``), ``slots = 1 + nsteps // saveEveryNsteps``.  ``v``: ``(n_pcof,)``, or
+    ``(n_pcof, n_vec)`` for a result with a trailing direction axis (DeviceProblem.eval_pushforward).  One
+    forward sweep and one forced scan on the device for all directions; exact for the discrete scheme, unlike differences of
+    the output calls.  Not in the reference."""
+    save = int(saveEveryNsteps)
+    if save < 1:
+        raise ValueError("saveEveryNsteps must be a positive integer")
+    # (refusals before a handle is made or anything is uploaded)
+    asked = pushforward_outputs(prob.N_tot_levels, output, level_map, observables)
+    pushforward_directions(v, len(np.asarray(pcof).reshape(-1)))
+    dp = device_problem(prob, order)
+    dp.set_controls(controls)
+    dp.set_save_every(save)
+    try:
+        out = dp.eval_pushforward(pcof, v, **asked)
+    finally:
+        dp.set_save_every(1)
+    return real_to_complex(out["states"]) if output == "states" else out[output]
 
 
 def eval_grad_forced(prob, controls, pcof, target, order=2, cost_type="Infidelity"):
