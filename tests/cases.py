@@ -92,6 +92,49 @@ def synthetic_case(qgd, N=100, c=20, n_ops=4, nsteps=24, tf=0.5, seed=5):
     return prob, ctrl, pcof, target
 
 
+# name -> (N, columns, control operators, order, time steps): the shapes of test_gpu_sensitivity_shapes.py, the smallest that reach
+# more than one column group (cp / 8 > 1), a last group with an odd number of columns, two and three 16-row blocks (Np = 32, 48),
+# padding rows inside a 64-row tile (N = 60) and dense operators at Np = 64.  DESIGN.md section 5 ("Shapes of the sensitivity
+# tests") says which reaches what.
+SENSITIVITY_RANDOM = {"rand21x11": (21, 11, 2, 4, 5), "rand40x20": (40, 20, 2, 6, 4), "rand60x9": (60, 9, 3, 4, 4),
+                      "rand64x17": (64, 17, 2, 8, 3)}
+SENSITIVITY_GUARDED = ("rand21x11", "rand40x20")
+SENSITIVITY_SHAPES = tuple(SENSITIVITY_RANDOM) + ("qutrits27", "levels543")
+
+
+def _three_transmons(qgd, sizes, nsteps, seed):
+    """cnot3's frequencies and couplings on other level counts, two carriers per control (n_pcof = 3 * 2 * 2 * 4 = 48)"""
+    freqs = 2 * np.pi * np.array([4.10595, 4.81526, 7.8447])
+    kerr = 2 * np.pi * np.array([[0.2198, 1e-6, 0.0025], [1e-6, 0.2252, 0.0025], [0.0025, 0.0025, 3e-5]])
+    prob = qgd.DispersiveProblem(sizes, (2, 2, 2), freqs, freqs, kerr, float(nsteps), nsteps, sparse_rep=False,
+                                 gmres_abstol=1e-15, gmres_reltol=1e-15)
+    ctrl = [qgd.CarrierControl(qgd.FortranBSplineControl(2, 4, prob.tf), [0.0, -kerr[k, k]]) for k in range(3)]
+    rng = np.random.default_rng(seed)
+    pcof = (rng.random(qgd.get_number_of_control_parameters(ctrl)) - 0.5) * 2 * np.pi * 0.02
+    return prob, ctrl, pcof, rand_target(prob, seed + 1)
+
+
+def sensitivity_case(qgd, name):
+    """(prob, ctrl, pcof, target, order) of one of SENSITIVITY_SHAPES.  The random ones are built as _rand_case of
+    test_gpu_state_transfer.py: construct_rand_prob(N, n_ops, scale = 1 / N) cut to c of its (random, distinct) columns, cubic
+    B-spline controls with n_pcof = 24; the guarded ones carry a nonzero diagonal guard matrix as test_gpu_scan_shapes.py's
+    problems do.  qutrits27: three qutrits with their guard projector (sparse operators at Np = 32); levels543: the (5, 4, 3)
+    problem of test_gpu_front.py::test_front_padded_problem (N = 60 in 64-row tiles, sparse operators, the fused front)."""
+    if name == "qutrits27":
+        return _three_transmons(qgd, (3, 3, 3), 5, 27) + (6,)
+    if name == "levels543":
+        return _three_transmons(qgd, (5, 4, 3), 6, 60) + (6,)
+    N, c, n_ops, order, nsteps = SENSITIVITY_RANDOM[name]
+    prob = qgd.construct_rand_prob(N, n_ops, tf=0.5, nsteps=nsteps, gmres_abstol=1e-15, gmres_reltol=1e-15, scale=1.0 / N)
+    prob.u0 = np.asfortranarray(prob.u0[:, :c]); prob.v0 = np.asfortranarray(prob.v0[:, :c]); prob.N_initial_conditions = c
+    rng = np.random.default_rng(1000 * N + c)
+    if name in SENSITIVITY_GUARDED:
+        prob.guard_subspace_projector = np.asfortranarray(np.diag(rng.random(2 * N)))
+    ctrl = [qgd.FortranBSplineControl(3, 12 // n_ops, prob.tf) for _ in range(n_ops)]
+    pcof = rng.standard_normal(qgd.get_number_of_control_parameters(ctrl))
+    return prob, ctrl, pcof, rng.random((N, c)) + 1j * rng.random((N, c)), order
+
+
 class SineControl:
     """A control that is NOT linear in its coefficients theta = (A, omega, phi): p(t) = A sin(omega t + phi),
     q(t) = A/2 cos(omega t + phi) -- the reference's AbstractControl protocol is open (Control.jl:6-27), its in-tree

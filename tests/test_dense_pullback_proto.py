@@ -51,7 +51,7 @@ def _parts(bars):
 
 
 @pytest.mark.parametrize("name,order,refine", [("cnot2", 2, 2), ("cnot2", 4, 3), ("cnot2", 8, 3), ("guarded", 6, 7),
-                                               ("cnot2", 16, 2)])
+                                               ("cnot2", 16, 2), ("rand21x11", 4, 3)])
 def test_proto_dense_pullback_matches_differences(qgd, name, order, refine):
     prob, ctrl, pcof, _ = _case(qgd, name)
     Gp, Gq, off = qgd.control_basis(ctrl, prob.nsteps, prob.tf, order // 2)

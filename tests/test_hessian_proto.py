@@ -13,6 +13,8 @@ CASES = [("cnot2", 2), ("cnot2", 4), ("cnot2", 8), ("guarded", 6), ("dense_guard
 def _case(qgd, name):
     if name == "cnot2":
         return cases.cnot2_case(qgd, nsteps=12, tf=12.0)
+    if name == "rand21x11":                       # N = 21 in two 16-row blocks, 11 columns in two groups, a diagonal guard matrix
+        return cases.sensitivity_case(qgd, name)[:4]
     if name == "dense_guard":
         return cases.dense_guard_case(qgd, nsteps=10, tf=5.0)
     return cases.guarded_case(qgd, nsteps=10, tf=5.0)

@@ -21,6 +21,7 @@ def _problem(qgd, name, guard):
 
 # (cnot2 has no guard levels: "guard" is the problem as it is, "noguard" the two guarded problems without their projector)
 PARAMS = [(name, order, True) for name, order in CASES] + [(name, order, False) for name, order in CASES if name != "cnot2"]
+PARAMS += [("rand21x11", 4, True), ("rand21x11", 4, False)]      # more than 8 columns, more than 16 levels (cases.sensitivity_case)
 
 
 @pytest.mark.parametrize("name,order,guard", PARAMS, ids=[f"{n}-{o}-{'guard' if g else 'noguard'}" for n, o, g in PARAMS])

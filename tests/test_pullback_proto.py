@@ -46,7 +46,7 @@ def _differences(prob, Gp, Gq, off, pcof, order, save, bars, h=1e-3):
 
 
 @pytest.mark.parametrize("name,order,save", [("cnot2", 2, 1), ("cnot2", 4, 1), ("cnot2", 8, 1), ("guarded", 6, 1),
-                                             ("cnot2", 4, 5)])
+                                             ("cnot2", 4, 5), ("rand21x11", 4, 1), ("rand21x11", 4, 2)])
 def test_proto_pullback_matches_differences(qgd, name, order, save):
     prob, ctrl, pcof, _ = _case(qgd, name)
     Gp, Gq, off = qgd.control_basis(ctrl, prob.nsteps, prob.tf, order // 2)

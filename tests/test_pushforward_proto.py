@@ -14,7 +14,7 @@ import proto_pushforward as pf
 from test_hessian_proto import _case
 from test_pullback_proto import _cotangents
 
-CASES = [("cnot2", 2), ("cnot2", 4), ("cnot2", 8), ("guarded", 6)]
+CASES = [("cnot2", 2), ("cnot2", 4), ("cnot2", 8), ("guarded", 6), ("rand21x11", 4)]
 
 
 def _parts(bars):
