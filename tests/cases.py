@@ -102,6 +102,20 @@ SENSITIVITY_GUARDED = ("rand21x11", "rand40x20")
 SENSITIVITY_SHAPES = tuple(SENSITIVITY_RANDOM) + ("qutrits27", "levels543")
 
 
+# name -> (N, columns, B-spline coefficients per carrier of each control operator, order, time steps, guarded): the shapes at which
+# the sensitivity kernels branch on the ORDER (m = order / 2 up to 8) and on the number of control operators (1, 4, 5, 8), with
+# coefficient counts that differ between the operators.  NB = 2 * n_ops * m is the number of basis directions of the second-order
+# entry points (at most 64): ops8o8 and ops4o16 sit on the last slot, ops5o14 (NB = 70) past it.  DESIGN.md section 5 says which
+# reaches what; tests/test_sensitivity_orders_proto.py holds what makes them meaningful (every Taylor level of the control basis
+# moves the reference by 1000 times the bound it is compared at).
+SENSITIVITY_ORDERS_RANDOM = {"ops8o8": (12, 5, (4, 5, 4, 4, 5, 4, 4, 5), 8, 4, True), "ops4o16": (20, 9, (4, 6, 5, 4), 16, 3, True),
+                             "ops1o16": (64, 3, (6,), 16, 3, False), "ops2o12": (64, 9, (5, 7), 12, 3, False),
+                             "ops5o12": (33, 10, (4, 5, 4, 6, 4), 12, 3, True), "ops5o14": (10, 3, (4, 5, 4, 6, 4), 14, 3, True)}
+SENSITIVITY_ORDER_SHAPES = ("ops8o8", "ops4o16", "ops1o16", "ops2o12", "ops5o12", "qutrits27o12", "levels543o10")
+SENSITIVITY_PAST_THE_DIRECTIONS = "ops5o14"
+CARRIER_FREQUENCIES = ([0.0, 5.0], [3.0], [0.0, -4.0, 7.0], [2.0, -6.0])
+
+
 def _three_transmons(qgd, sizes, nsteps, seed):
     """cnot3's frequencies and couplings on other level counts, two carriers per control (n_pcof = 3 * 2 * 2 * 4 = 48)"""
     freqs = 2 * np.pi * np.array([4.10595, 4.81526, 7.8447])
@@ -115,7 +129,8 @@ def _three_transmons(qgd, sizes, nsteps, seed):
 
 
 def sensitivity_case(qgd, name):
-    """(prob, ctrl, pcof, target, order) of one of SENSITIVITY_SHAPES.  The random ones are built as _rand_case of
+    """(prob, ctrl, pcof, target, order) of one of SENSITIVITY_SHAPES, SENSITIVITY_ORDER_SHAPES or SENSITIVITY_PAST_THE_DIRECTIONS
+    (the latter two: _orders_case and the two qudit problems at orders 12 and 10).  The random ones of SENSITIVITY_SHAPES are built as _rand_case of
     test_gpu_state_transfer.py: construct_rand_prob(N, n_ops, scale = 1 / N) cut to c of its (random, distinct) columns, cubic
     B-spline controls with n_pcof = 24; the guarded ones carry a nonzero diagonal guard matrix as test_gpu_scan_shapes.py's
     problems do.  qutrits27: three qutrits with their guard projector (sparse operators at Np = 32); levels543: the (5, 4, 3)
@@ -124,6 +139,12 @@ def sensitivity_case(qgd, name):
         return _three_transmons(qgd, (3, 3, 3), 5, 27) + (6,)
     if name == "levels543":
         return _three_transmons(qgd, (5, 4, 3), 6, 60) + (6,)
+    if name == "qutrits27o12":                    # (the same two problems above the fused front's order 8)
+        return _three_transmons(qgd, (3, 3, 3), 5, 27) + (12,)
+    if name == "levels543o10":
+        return _three_transmons(qgd, (5, 4, 3), 6, 60) + (10,)
+    if name in SENSITIVITY_ORDERS_RANDOM:
+        return _orders_case(qgd, name)
     N, c, n_ops, order, nsteps = SENSITIVITY_RANDOM[name]
     prob = qgd.construct_rand_prob(N, n_ops, tf=0.5, nsteps=nsteps, gmres_abstol=1e-15, gmres_reltol=1e-15, scale=1.0 / N)
     prob.u0 = np.asfortranarray(prob.u0[:, :c]); prob.v0 = np.asfortranarray(prob.v0[:, :c]); prob.N_initial_conditions = c
@@ -131,6 +152,23 @@ def sensitivity_case(qgd, name):
     if name in SENSITIVITY_GUARDED:
         prob.guard_subspace_projector = np.asfortranarray(np.diag(rng.random(2 * N)))
     ctrl = [qgd.FortranBSplineControl(3, 12 // n_ops, prob.tf) for _ in range(n_ops)]
+    pcof = rng.standard_normal(qgd.get_number_of_control_parameters(ctrl))
+    return prob, ctrl, pcof, rng.random((N, c)) + 1j * rng.random((N, c)), order
+
+
+def _orders_case(qgd, name):
+    """One of SENSITIVITY_ORDERS_RANDOM, built as the random shapes of sensitivity_case (same seeds, same order of the draws) on
+    tf = 1.5.  Control k is a cubic B-spline under the carriers CARRIER_FREQUENCIES[k % 4]: a cubic B-spline alone has no time
+    derivative from the fourth on, with carriers every Taylor level d = 0 .. m - 1 of the control basis is nonzero; the
+    coefficient counts and the carrier counts differ between the operators, so that an operator's offset into pcof, into the
+    gradient or into the basis tables taken from another operator does not land on itself."""
+    N, c, ncoef, order, nsteps, guarded = SENSITIVITY_ORDERS_RANDOM[name]
+    prob = qgd.construct_rand_prob(N, len(ncoef), tf=1.5, nsteps=nsteps, gmres_abstol=1e-15, gmres_reltol=1e-15, scale=1.0 / N)
+    prob.u0 = np.asfortranarray(prob.u0[:, :c]); prob.v0 = np.asfortranarray(prob.v0[:, :c]); prob.N_initial_conditions = c
+    rng = np.random.default_rng(1000 * N + c)
+    if guarded:
+        prob.guard_subspace_projector = np.asfortranarray(np.diag(rng.random(2 * N)))
+    ctrl = [qgd.CarrierControl(qgd.FortranBSplineControl(3, nc, prob.tf), CARRIER_FREQUENCIES[k % 4]) for k, nc in enumerate(ncoef)]
     pcof = rng.standard_normal(qgd.get_number_of_control_parameters(ctrl))
     return prob, ctrl, pcof, rng.random((N, c)) + 1j * rng.random((N, c)), order
 

@@ -5,6 +5,14 @@ of columns, two and three 16-row blocks (Np = 32 and 48), N = 60 in 64-row tiles
 Np = 32, and the fused front with padding rows.  The problems are cases.sensitivity_case's; DESIGN.md section 5 ("Shapes of the
 sensitivity tests") lists which shape reaches which branch.
 
+The same tests run at cases.SENSITIVITY_ORDER_SHAPES, where the kernels branch on the order and on the control operators: orders
+10 .. 16 (m = 5 .. 8: past the fused front's m <= 4, past launch_gradpoint64_m's m <= 5, the ELL kernels' and the sweep kernels'
+last m = 8, 144 KB of LDS in k_forced_basis at Np = 64), 1, 4, 5 and 8 control operators (DISPATCH_NOPS cases 1 and 4, the
+generic instantiation) with coefficient counts that differ between the operators, and NB = 2 n_ops m = 64 basis directions, the
+last slot of k_hvp_forcing and k_hess_sigma.  Their controls are B-splines under carriers; tests/test_sensitivity_orders_proto.py
+asserts on the CPU that every Taylor level of the control basis moves these references by 1000 times the bounds below.  Section 10
+is one problem past the 64 directions (NB = 70), section 11 one past the 8 operators.
+
 Every comparison is against a numpy statement of tests/ (proto_propagator, proto_hessian, proto_hvp, proto_pullback,
 proto_pushforward, proto_dense_pullback), computed once per shape and shared; the device is compared with itself only where the
 claim is that two calls give the same bits.  Direction counts differ from the group counts (3 directions beside 2 groups, 2 beside
@@ -30,6 +38,7 @@ import cases
 import proto_dense_pullback as pdp
 import proto_hessian as ph
 import proto_hvp as pv
+import proto_propagator as pp
 import proto_pullback as pb
 import proto_pushforward as pf
 from test_gpu_hessian import _handle
@@ -38,12 +47,14 @@ from test_gpu_pullback import _hermitian
 
 pytestmark = pytest.mark.gpu
 
-NAMES = cases.SENSITIVITY_SHAPES
+NAMES = cases.SENSITIVITY_SHAPES + cases.SENSITIVITY_ORDER_SHAPES      # (appended: the indices of the first six stay)
 shapes = pytest.mark.parametrize("k", range(len(NAMES)), ids=NAMES)
 REFINE = 3
 L2_SHAPE = NAMES.index("rand40x20")            # (the route that does not fit in LDS: three groups, three row blocks)
 SAVE_SHAPE = NAMES.index("rand21x11")          # (save_every = 2 on 5 steps: slots 0, 2, 4, the odd last column group)
 FRONT_SHAPE = NAMES.index("levels543")
+ABOVE_THE_FRONT = (NAMES.index("qutrits27o12"), NAMES.index("levels543o10"))      # (the qudit problems at m = 6 and 5: the front has m <= 4)
+PAST_THE_DIRECTIONS = cases.SENSITIVITY_PAST_THE_DIRECTIONS
 _cache = {}
 
 
@@ -56,10 +67,11 @@ def _shape(qgd, k):
     sweep) is computed at first use, once, and read only."""
     if k in _cache:
         return _cache[k]
-    prob, ctrl, pcof, target, order = cases.sensitivity_case(qgd, NAMES[k])
+    name, seed = (k, 7100) if isinstance(k, str) else (NAMES[k], 7000 + k)      # (by name: the problem past the direction limit)
+    prob, ctrl, pcof, target, order = cases.sensitivity_case(qgd, name)
     N, c, nt = prob.N_tot_levels, prob.N_initial_conditions, prob.nsteps + 1
-    rng = np.random.default_rng(7000 + k)
-    s = types.SimpleNamespace(name=NAMES[k], prob=prob, ctrl=ctrl, pcof=pcof, target=target, order=order, N=N, c=c, nt=nt,
+    rng = np.random.default_rng(seed)
+    s = types.SimpleNamespace(name=name, prob=prob, ctrl=ctrl, pcof=pcof, target=target, order=order, N=N, c=c, nt=nt,
                               n_vec=_n_vec(c), lm=rng.standard_normal((4, N)), oc=_hermitian(rng, 2, N),
                               orl=_hermitian(rng, 1, N, False))
     s.V = rng.standard_normal((len(pcof), s.n_vec))
@@ -140,7 +152,7 @@ def _open(qgd, s):
 
 def _assert_paths(s, paths):
     """what the shape is there for: dense operators on the random problems, the ELL kernels on the qudit problems"""
-    want = ["dense"] if s.name.startswith("rand") else ["dense", "sparse"]
+    want = ["dense"] if s.name.startswith(("rand", "ops")) else ["dense", "sparse"]
     assert paths == want, (s.name, paths)
 
 
@@ -186,6 +198,7 @@ def test_gradients(qgd, k, monkeypatch):
     try:
         for path in _paths(qgd, dp):
             g = dp.discrete_adjoint(s.pcof)[0]
+            assert k not in ABOVE_THE_FRONT or not dp.front_path_taken()
             _relative(g, g0, 1e-10, f"{s.name} {path}: discrete_adjoint vs proto_propagator.evaluate")
             _relative(dp.eval_grad_forced(s.pcof), g, 1e-12, f"{s.name} {path}: eval_grad_forced vs discrete_adjoint")
         if k == FRONT_SHAPE:
@@ -321,26 +334,35 @@ def test_pushforward(qgd, k):
 
 # -- 7: dense output ----------------------------------------------------------------------------------------------------------------
 
-@shapes
-def test_dense_output_and_its_pullback(qgd, k):
-    s = _shape(qgd, k)
+def _dense_refs(qgd, s):
     S, P, E = pdp.dense_outputs(qgd, s.prob, *s.basis, s.pcof, s.order, REFINE, None, s.oc)
     _, Pm, Er = pdp.dense_outputs(qgd, s.prob, *s.basis, s.pcof, s.order, REFINE, s.lm, s.orl)
     parts = _bars(s, 1 + s.prob.nsteps * REFINE, 700)
     parts["all three at once"] = _together(parts)
     refs = {what: pdp.dense_pullback(qgd, s.prob, *s.basis, s.pcof, s.order, REFINE, fwd=s.fwd, **_proto(part))
             for what, part in parts.items()}
+    return (S, P, E, Pm, Er), parts, refs
+
+
+def _dense_outputs_and_pullbacks(dp, s, outputs, parts, refs, label):
+    S, P, E, Pm, Er = outputs
+    _close(dp.eval_dense_states(REFINE, s.pcof), S, f"{label}: eval_dense_states")
+    _close(dp.eval_dense_populations(REFINE, s.pcof), P, f"{label}: eval_dense_populations")
+    _close(dp.eval_dense_populations(REFINE, s.pcof, level_map=s.lm), Pm, f"{label}: eval_dense_populations with a 4-row map")
+    _close(dp.eval_dense_expectations(REFINE, s.oc, s.pcof), E, f"{label}: eval_dense_expectations of 2 complex observables")
+    _close(dp.eval_dense_expectations(REFINE, s.orl, s.pcof), Er, f"{label}: eval_dense_expectations of 1 real observable")
+    for what, part in parts.items():
+        _close(dp.eval_dense_pullback(REFINE, s.pcof, **part), refs[what], f"{label}: dense pullback, {what}")
+
+
+@shapes
+def test_dense_output_and_its_pullback(qgd, k):
+    s = _shape(qgd, k)
+    outputs, parts, refs = _dense_refs(qgd, s)
     dp = _open(qgd, s)
     try:
         for path in _paths(qgd, dp):
-            label = f"{s.name} {path} refine {REFINE}"
-            _close(dp.eval_dense_states(REFINE, s.pcof), S, f"{label}: eval_dense_states")
-            _close(dp.eval_dense_populations(REFINE, s.pcof), P, f"{label}: eval_dense_populations")
-            _close(dp.eval_dense_populations(REFINE, s.pcof, level_map=s.lm), Pm, f"{label}: eval_dense_populations with a 4-row map")
-            _close(dp.eval_dense_expectations(REFINE, s.oc, s.pcof), E, f"{label}: eval_dense_expectations of 2 complex observables")
-            _close(dp.eval_dense_expectations(REFINE, s.orl, s.pcof), Er, f"{label}: eval_dense_expectations of 1 real observable")
-            for what, part in parts.items():
-                _close(dp.eval_dense_pullback(REFINE, s.pcof, **part), refs[what], f"{label}: dense pullback, {what}")
+            _dense_outputs_and_pullbacks(dp, s, outputs, parts, refs, f"{s.name} {path} refine {REFINE}")
     finally:
         dp.close()
 
@@ -401,3 +423,54 @@ def test_refusals_at_65_levels(qgd):
             assert np.array_equal(dp.discrete_adjoint(pcof)[0], g0), what
     finally:
         dp.close()
+
+
+# -- 10: past the limit of 64 basis directions --------------------------------------------------------------------------------------
+
+def test_past_64_basis_directions(qgd):
+    """5 operators at order 14: NB = 2 * 5 * 7 = 70 basis directions.  The entry points that keep one value per direction in 64
+    slots (eval_hessian, eval_hessian_vec, eval_pushforward) refuse with QGD_ERR_UNSUPPORTED and leave the handle working; the
+    ones without that limit -- both gradients, the pullback, the dense pullback, the forward and dense outputs -- are compared
+    with their statements on the same handle, at the bounds of sections 1, 2, 5 and 7."""
+    s = _shape(qgd, PAST_THE_DIRECTIONS)
+    assert 2 * s.prob.N_operators * (s.order // 2) == 70
+    g0 = pp.evaluate(s.prob, *s.basis, s.pcof, s.target, s.order)["grad"]
+    dense = _dense_refs(qgd, s)
+    dp = _open(qgd, s)
+    try:
+        first = dp.discrete_adjoint(s.pcof)[0]
+        for what, call in (("eval_hessian", lambda: dp.eval_hessian(s.pcof)),
+                           ("eval_hessian_vec", lambda: dp.eval_hessian_vec(s.pcof, s.V[:, 0])),
+                           ("eval_hessian_vec of a batch", lambda: dp.eval_hessian_vec(s.pcof, s.V)),
+                           ("eval_pushforward", lambda: dp.eval_pushforward(s.pcof, s.V, states=True))):
+            with pytest.raises(qgd._lib.QGDError) as ei:
+                call()
+            assert ei.value.code == qgd._lib.QGD_ERR_UNSUPPORTED, (what, ei.value.code)
+            assert dp.lib.qgd_last_error(dp.h).decode(), what
+            assert np.array_equal(dp.discrete_adjoint(s.pcof)[0], first), what
+        paths = []
+        for path in _paths(qgd, dp):
+            paths.append(path)
+            label = f"{s.name} {path}"
+            g = dp.discrete_adjoint(s.pcof)[0]
+            _relative(g, g0, 1e-10, f"{label}: discrete_adjoint vs proto_propagator.evaluate")
+            _relative(dp.eval_grad_forced(s.pcof), g, 1e-12, f"{label}: eval_grad_forced vs discrete_adjoint")
+            _forward_outputs(dp, s, label)
+            _pullbacks(dp, s, 1, label)
+            _dense_outputs_and_pullbacks(dp, s, *dense, f"{label} refine {REFINE}")
+        _assert_paths(s, paths)
+    finally:
+        dp.close()
+
+
+# -- 11: past the limit of 8 control operators --------------------------------------------------------------------------------------
+
+def test_nine_control_operators_are_refused(qgd):
+    """The kernels hold the coefficients of at most 8 control operators (QGD_MAX_OPS_DEV): a ninth is refused when the handle is
+    made, 8 are taken."""
+    prob = qgd.construct_rand_prob(6, 9, tf=1.0, nsteps=3)
+    with pytest.raises(qgd._lib.QGDError) as ei:
+        qgd.DeviceProblem(prob, 4)
+    assert ei.value.code == qgd._lib.QGD_ERR_UNSUPPORTED
+    assert "8 control operators" in str(ei.value)
+    qgd.DeviceProblem(qgd.construct_rand_prob(6, 8, tf=1.0, nsteps=3), 4).close()
