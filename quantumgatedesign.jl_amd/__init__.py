@@ -20,6 +20,7 @@ from .evolution import (DeviceProblem, device_problem, clear_cache, release, eva
                         discrete_adjoint_batch, eval_objective_batch, batch_pcofs, finite_difference_points, finite_difference_quotient,
                         discrete_adjoint_, infidelity, infidelity_real, state_transfer_infidelity, COST_TYPES, guard_penalty_real, complex_to_real,
                         real_to_complex)
+from .ensemble import Ensemble, EnsembleResult, EnsembleObjective, ensemble_reduce, eval_ensemble, discrete_adjoint_ensemble
 from .distributed import (DeviceBackend, TimePartitioned, TorchComm, LocalGroup, ColumnBackend, ColumnSharded,
                           RcclEvaluation, comm_unique_id)
 from .optimize import optimize_gate, OptimizationHistory, read_optimization_history

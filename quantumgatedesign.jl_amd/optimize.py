@@ -90,14 +90,19 @@ class _Stop(Exception):
 
 def optimize_gate(schro_prob, controls, pcof_init, target, order=4, pcof_L=None, pcof_U=None, maxIter=50,
                   print_level=5, ridge_penalty_strength=1e-2, max_cpu_time=60.0 * 60 * 24, filename=None,
-                  cost_type="Infidelity"):
+                  cost_type="Infidelity", ensemble=None):
     """optimize_gate(prob, controls, pcof_init, target; order=4, pcof_L, pcof_U, maxIter=50,
     print_level=5, ridge_penalty_strength=1e-2, max_cpu_time) -> OptimizationHistory.
 
     ``cost_type`` (not in the reference's optimize_gate): what the final state is measured by, one of ``COST_TYPES``.
     With a type other than ``Infidelity`` the objective is cost + guard penalty + ridge penalty with the cost the
     device returns (``StateTransfer``: the per-column infidelity), the history's ``infidelity`` column holds that cost,
-    and the result file's ``Setup`` group names the type."""
+    and the result file's ``Setup`` group names the type.
+
+    ``ensemble`` (an ``Ensemble``; not in the reference's optimize_gate either): the robust objective -- the weighted mean
+    of the cost over the members + the weighted mean of the guard penalty + ridge penalty, every member evaluated on a handle
+    of its own and reduced by ``ensemble_reduce`` (``ensemble.py``).  The history's ``infidelity`` / ``guard_penalty`` columns hold the two
+    means; ``Setup`` gains ``ensemble_weights`` and ``ensemble_members``.  None: nothing changes."""
     from scipy.optimize import minimize
 
     if COST_TYPES.get(str(cost_type)) is None:
@@ -108,9 +113,11 @@ def optimize_gate(schro_prob, controls, pcof_init, target, order=4, pcof_L=None,
     N_coeff = get_number_of_control_parameters(controls)
     if len(pcof_init) != N_coeff:
         raise ValueError("length of pcof_init does not match the controls")          # :203
-    dp = device_problem(schro_prob, order)
-    dp.set_controls(controls)
-    dp.set_target(target)
+    dp = None
+    if ensemble is None:      # (an ensemble evaluates its members' handles, never the nominal one)
+        dp = device_problem(schro_prob, order)
+        dp.set_controls(controls)
+        dp.set_target(target)
     hist = OptimizationHistory()
     last = {}
     t0 = time.time()
@@ -130,13 +137,23 @@ def optimize_gate(schro_prob, controls, pcof_init, target, order=4, pcof_L=None,
         setup["pcof_U"] = np.broadcast_to(np.asarray(pcof_U, float), (N_coeff,)).copy()
     if not plain:      # (only then: files of the default type stay as they were)
         setup["cost_type"] = str(cost_type).lstrip(":")
+    robust = None
+    if ensemble is not None:
+        from .ensemble import EnsembleObjective
+        robust = EnsembleObjective(schro_prob, controls, target, ensemble, order, cost_type)
+        setup["ensemble_weights"] = np.asarray(ensemble.effective_weights(), dtype=np.float64)
+        setup["ensemble_members"] = int(ensemble.K)
 
     def fun(pcof):
-        grad, out3 = dp.discrete_adjoint(pcof)                                       # :257-268, :304
-        if plain:
-            infid = 1.0 - (out3[0] ** 2 + out3[1] ** 2) / schro_prob.N_ess_levels ** 2   # infidelity.jl:17
+        if robust is not None:
+            grad, infid, guard = robust(pcof)              # the means over the members, and the gradient of their sum
+            out3 = (infid, 0.0, guard)
         else:
-            infid = float(out3[0])                                                   # { cost, 0, guard penalty }
+            grad, out3 = dp.discrete_adjoint(pcof)                                   # :257-268, :304
+            if plain:
+                infid = 1.0 - (out3[0] ** 2 + out3[1] ** 2) / schro_prob.N_ess_levels ** 2   # infidelity.jl:17
+            else:
+                infid = float(out3[0])                                               # { cost, 0, guard penalty }
         ridge = float(pcof @ pcof) * ridge_penalty_strength / len(pcof)              # :272
         grad = grad + 2.0 * ridge_penalty_strength * pcof / len(pcof)                # :311
         obj = infid + out3[2] + ridge
@@ -166,7 +183,8 @@ def optimize_gate(schro_prob, controls, pcof_init, target, order=4, pcof_L=None,
 
     bounds = list(zip(bound(pcof_L, -np.inf), bound(pcof_U, np.inf)))                # :385-403
     res = None
-    dp.set_cost_type(cost_type)
+    if dp is not None:
+        dp.set_cost_type(cost_type)
     try:
         try:
             res = minimize(fun, pcof_init, jac=True, method="L-BFGS-B", bounds=bounds, callback=callback,
@@ -176,7 +194,8 @@ def optimize_gate(schro_prob, controls, pcof_init, target, order=4, pcof_L=None,
         if res is not None and not np.array_equal(res.x, last["pcof"]):
             fun(np.asarray(res.x, dtype=np.float64))       # make `last` describe the returned iterate
     finally:
-        dp.set_cost_type("Infidelity")
+        if dp is not None:
+            dp.set_cost_type("Infidelity")
     if not len(hist) or not np.array_equal(hist.pcof[-1], last["pcof"]):
         hist.iter_count.append(len(hist.iter_count)); hist.ipopt_obj_value.append(last["obj"])
         hist.wall_time.append(time.time() - t0); hist.pcof.append(last["pcof"])

@@ -1,0 +1,92 @@
+"""What an ensemble evaluation costs: cnot2 at the benchmark shape (order 8, 100 steps), one process, the
+protocol of scripts/batch_timing.py.  For K = 1, 4, 16, 64, 256 members (detuned copies of the problem):
+  (a) a Python loop over K handles, one per member: DeviceProblem.discrete_adjoint on each, then ensemble_reduce on the host
+  (b) discrete_adjoint_ensemble, the functional form: the same loop behind device_problem's cache (controls, target and cost
+      type are looked at on every member of every call)
+The routes alternate inside every round; every call ends in a host wait for its results, so the host clock around `reps`
+repetitions is the time of the work.  Reported: median and min..max over the rounds of the time per call.
+
+    timeout 300 python scripts/ensemble_timing.py [--rounds 9] [--out FILE.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
+from __graft_entry__ import import_package
+import cases
+
+KS = (1, 4, 16, 64, 256)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.rounds < 7:
+        ap.error("at least 7 rounds")
+    if not torch.cuda.is_available():
+        sys.exit("ensemble_timing.py measures on the GPU: none found")
+    qgd = import_package()
+    prob, ctrl, pcof, target = cases.cnot2_case(qgd, nsteps=100, tf=100.0, amp=1e-2)
+    N, Kmax = prob.N_tot_levels, max(KS)
+    shift = np.linspace(-0.02, 0.02, Kmax)[:, None, None] * np.diag(np.arange(N, dtype=float))
+    full = qgd.Ensemble(prob.system_sym[None] + shift, np.repeat(prob.system_asym[None], Kmax, axis=0))
+    singles = []
+    for k in range(Kmax):
+        h = qgd.DeviceProblem(full.member_problem(prob, k), 8); h.set_controls(ctrl); h.set_target(target); h.set_timing(0)
+        singles.append(h)
+    n_ess = prob.N_ess_levels
+
+    def loop(K, ens):
+        res = [singles[k].discrete_adjoint(pcof) for k in range(K)]
+        return qgd.ensemble_reduce(np.array([g for g, _ in res]), np.array([np.asarray(o) for _, o in res]), None, "Infidelity", n_ess)
+
+    def functional(K, ens):
+        return qgd.discrete_adjoint_ensemble(prob, ctrl, pcof, target, ens, order=8)
+
+    def clock(fn, K, ens, reps):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn(K, ens)
+        return (time.perf_counter() - t0) / reps
+
+    out = []
+    for K in KS:
+        ens = qgd.Ensemble(full.system_sym[:K], full.system_asym[:K])
+        g, c, gd = loop(K, ens)                                # what is timed is what the tests compare: the same bits either way
+        r = functional(K, ens)
+        assert np.array_equal(g, r.grad) and (c, gd) == (r.cost, r.guard)
+        reps = max(2, 512 // K)
+        for fn in (loop, functional):
+            clock(fn, K, ens, 2)
+        t = {"loop": [], "functional": []}
+        for _ in range(args.rounds):
+            t["loop"].append(clock(loop, K, ens, reps)); t["functional"].append(clock(functional, K, ens, reps))
+        stat = lambda x: [statistics.median(x) * 1e6, min(x) * 1e6, max(x) * 1e6]
+        out.append({"K": K, "reps": reps, "rounds": args.rounds, "loop_us": stat(t["loop"]), "functional_us": stat(t["functional"])})
+        ens.release_members(prob)
+    for h in singles:
+        h.close()
+    box = torch.cuda.get_device_name(0)
+    print(f"cnot2, order 8, 100 steps, {len(pcof)} coefficients; {box}; {args.rounds} rounds, median (min..max) in us")
+    print("| K | (a) K handles + host reduction, us | (a) per member, us | (b) discrete_adjoint_ensemble, us | (b) per member, us |")
+    print("|---|---|---|---|---|")
+    for r in out:
+        a, b = r["loop_us"], r["functional_us"]
+        print(f"| {r['K']} | {a[0]:.0f} ({a[1]:.0f}..{a[2]:.0f}) | {a[0] / r['K']:.1f} | {b[0]:.0f} ({b[1]:.0f}..{b[2]:.0f}) | {b[0] / r['K']:.1f} |")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"device": box, "n_pcof": int(len(pcof)), "rows": out}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
