@@ -2,9 +2,9 @@
 // launch macros, the phase timer and the internal entry points of each unit.
 //   qgd_host_alloc.cpp    handles: creation, validation (SchrodingerProb.jl:73-154), the time grid and its windows, setters
 //   qgd_host_eval.cpp     one evaluation: forward / adjoint phases, result transport, the evaluation entry points
-//   qgd_host_sens.cpp     sensitivities of the state to the parameters: the forced gradient, the exact Hessian, Hessian-vector products, pullbacks (grid points and dense output)
+//   qgd_host_sens.cpp     sensitivities of the state to the parameters: the forced gradient, the exact Hessian, Hessian-vector products, pullbacks (grid points and dense output); the refusals and the sweep they share with the pushforward
 //   qgd_host_pushforward.cpp  directional derivatives of the trajectory outputs (include/qgd_pushforward.h)
-//   qgd_host_output.cpp   reference-layout output arrays of a resident or windowed grid: the copy stream, staging, the one transport
+//   qgd_host_output.cpp   reference-layout output arrays of a resident or windowed grid: the copy stream, staging, the one transport; the rules of an OutputSelection
 //   qgd_host_windows.cpp  time grids in bounded memory: window entry, the windowed forward and adjoint passes
 //   qgd_host_comm.cpp     several GPUs: the RCCL binding, the collective evaluation and its failure mode
 // There is no CPU fallback: without a GPU every compute entry point fails.
@@ -149,14 +149,11 @@ struct qgd_handle_s {
     // qgd_eval_dense: the interpolated panels [1 + (points-1) refine][Np][2cp] of a resident grid or of the
     // longest window, and the weight table of qgd_k_interp.hip with its host copy (the upload reads it)
     double *dense_panels = nullptr, *dense_w = nullptr;
-    // qgd_eval_dense_pullback: the cotangents of the dense panels (G) and of the state and stage
-    // derivatives of every time point (gbar), the forcing, y and mu of its adjoint sweep, sigma / cpart / gradient / scalars of
-    // its own and the caller's cotangents, level map and observable planes on the device -- nothing shared with the pullback
-    // or the Hessian-vector setup above; the dense panels and the weight table are POOL_DENSE's, under that pool's key
-    struct DensePullbackBufs {
-        double *G = nullptr, *gbar = nullptr, *F = nullptr, *Y = nullptr, *mu = nullptr, *sigma = nullptr, *cpart = nullptr, *gB = nullptr, *scal = nullptr;
-        double *sbar = nullptr, *pbar = nullptr, *map = nullptr, *ebar = nullptr, *planes = nullptr;
-    } dpb;
+    // qgd_eval_dense_pullback: a set of the pullback's buffers of its own -- nothing shared with the
+    // pullback or the Hessian-vector setup above -- and in front of them the cotangents of the dense panels (G) and of the state
+    // and stage derivatives of every time point (gbar), sigma and cpart; the dense panels and the weight table are POOL_DENSE's,
+    // under that pool's key
+    struct DensePullbackBufs : PullbackBufs { double *G = nullptr, *gbar = nullptr, *sigma = nullptr, *cpart = nullptr; } dpb;
     // qgd_eval_pushforward: the tangent history sv of the directions of one chunk side by side, the scan
     // buffers and the direction table of that width, the one-operator bases {0 | w, 0} of every width w up to the chunk's, the
     // chunk's directions, the staged outputs and the caller's level map and observable planes on the device -- nothing shared
@@ -453,14 +450,27 @@ struct RcclApi {
 
 RcclApi &rccl();
 
+// Which trajectory outputs a call has, with which level map and which observables: what qgd_eval_populations,
+// qgd_eval_expectations and qgd_eval_dense (one output selected), the two pullbacks and qgd_eval_pushforward (the outputs whose
+// array is non-NULL) take from the caller.  The rules that follow from it alone are stated once, in qgd_host_output.cpp:
+// selection_refusals (in front of ENTER), output_sizes (with `sc` slots x columns), upload_selection (on k.stream).
+struct OutputSelection {
+    bool states = false, pops = false, expect = false;
+    const double *level_map = nullptr; int32_t n_groups = 0;
+    const double *obs_re = nullptr, *obs_im = nullptr; int32_t n_obs = 0;
+    bool with_map() const { return pops && level_map; }      // the populations are contracted with the map
+    bool with_im() const { return expect && obs_im; }        // imaginary planes behind the real ones
+};
+// doubles of each output (0: not selected), of the level map, of one set of observable planes and of all of them
+struct OutputSizes { size_t states, pops, expect, map, plane, planes; };
+
 // What qgd_eval_states / qgd_eval_populations / qgd_eval_expectations take out of the state panels of a sweep: the states
 // themselves [2N, slots, c], the level populations [N, slots, c] (n_groups = 0) or their contraction with the level map on the
 // device [n_groups, slots, c], or the expectation values [n_obs, slots, c] of the observables whose planes lie in obs_planes
 // (obs_im: imaginary planes behind the real ones)
 // refine = 0: of the grid points, every qgd_set_save_every-th (the three calls above).  refine = r >= 1 (qgd_eval_dense): of the
 // Hermite dense output, slot k at time k dt / r, every slot whatever qgd_set_save_every says; r = 1 is the grid points themselves
-enum ObserveKind { OBS_STATES, OBS_POPULATIONS, OBS_EXPECTATIONS };
-struct Observe { ObserveKind kind; int n_groups; double *out; int n_obs; bool obs_im; int refine = 0; };
+struct Observe { OutputSelection sel; double *out; int refine = 0; };      // (sel: one output selected)
 
 // qgd_host_alloc.cpp
 void free_pool(std::vector<void *> &pool);
@@ -475,8 +485,13 @@ int alloc_grid(qgd_handle h);
 // qgd_host_sens.cpp
 int forced_buffers(qgd_handle h, size_t nt, size_t B);
 size_t forced_missing(qgd_handle h);
+int trajectory_refusals(qgd_handle h, const std::string &name, const char *what, const double *pcof, int n_pcof, int history_precomputed, bool basis_bound);
+int pullback_sweep(qgd_handle h, const double *pcof, int n_pcof, int history_precomputed);
 
 // qgd_host_output.cpp
+int selection_refusals(qgd_handle h, const OutputSelection &s, const char *subject, const char *tail = "");
+OutputSizes output_sizes(const OutputSelection &s, size_t N, size_t sc);
+int upload_selection(qgd_handle h, const OutputSelection &s, const OutputSizes &z, double *map, double *planes);
 qgd_handle_s::HostReg *find_reg(qgd_handle h, const void *p, size_t bytes);
 int finish_copies(qgd_handle h);
 int grow_stage(qgd_handle h, Grown &g, size_t need);

@@ -430,7 +430,7 @@ static int forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, cons
             K_TRY(h, qgdk_forcing_add_derivs(&k));     // w_j = D_j w_0 + E_j
             if ((rc = history_out(h, uv_history, h->save_every))) return rc;
         }
-        if (states && (rc = observe_out(h, Observe{OBS_STATES, 0, states}, h->save_every))) return rc;
+        if (states && (rc = observe_out(h, Observe{{true}, states}, h->save_every))) return rc;
     }
     { PhaseTimer t(h, "terminal"); K_TRY(h, qgdk_terminal(&k, k.have_target)); }
     if ((rc = fetch_results(h, nullptr, out3))) { (void)finish_copies(h); return rc; }
@@ -557,12 +557,16 @@ int qgd_eval_forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, co
 
 
 // The forward sweep (or, history_precomputed under the rule of qgd_discrete_adjoint, the stored one) and nothing of it but what
-// `obs` names.  The sweep record ends as qgd_eval_forward without an output array leaves it.  (refuse_reuse: every caller has
-// asked already, before its uploads.)
+// `obs` names, behind the upload of its level map or observable planes into the staging pool.  The sweep record ends as
+// qgd_eval_forward without an output array leaves it.  (refuse_reuse: every caller has asked already, before the uploads.)
 static int observe_eval(qgd_handle h, const double *pcof, int n_pcof, int history_precomputed, const Observe &obs, double *out3)
 {
     qgdk_ctx &k = h->k;
     int rc;
+    const OutputSizes z = output_sizes(obs.sel, (size_t)k.N, 0);
+    if (z.map && (rc = grow_stage(h, h->obs_map, z.map))) return rc;
+    if (z.planes && (rc = grow_stage(h, h->obs_planes, z.planes))) return rc;
+    if ((rc = upload_selection(h, obs.sel, z, h->obs_map.p, h->obs_planes.p))) return rc;
     const int save = obs.refine ? 1 : h->save_every;      // (the dense output returns every sub-point)
     if (h->chunks_eff > 1) {      // one window is resident at a time: the pass over the windows is redone, each hands out its share
         if ((rc = chunked_forward(h, pcof, n_pcof, nullptr, save, &obs))) return rc;
@@ -585,48 +589,42 @@ int qgd_eval_states(qgd_handle h, const double *pcof, int32_t n_pcof, const doub
     ENTER(h, ENTER_KEEPS_GRAPH);
     if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_states is single-GPU: this handle has a communicator or a partition");
     if (forcing) { drop_graph(h); return forward_forced(h, pcof, n_pcof, forcing, nullptr, states, out3); }
-    return observe_eval(h, pcof, n_pcof, 0, Observe{OBS_STATES, 0, states}, out3);
+    return observe_eval(h, pcof, n_pcof, 0, Observe{{true}, states}, out3);
 }
 
 
 int qgd_eval_populations(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
                          const double *level_map, int32_t n_groups, double *populations, double *out3)
 {
+    const Observe obs{{false, true, false, level_map, n_groups}, populations};
     if (!populations) return fail(h, QGD_ERR_ARGUMENT, "null output array");
-    if (level_map && n_groups < 1) return fail(h, QGD_ERR_ARGUMENT, "a level map needs n_groups >= 1");
+    int rc;
+    if ((rc = selection_refusals(h, obs.sel, "qgd_eval_populations"))) return rc;
     ENTER(h, ENTER_KEEPS_GRAPH);
     if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_populations is single-GPU: this handle has a communicator or a partition");
-    int rc;
     if ((rc = refuse_reuse(h, history_precomputed))) return rc;
-    if (level_map) {
-        const size_t len = (size_t)n_groups * h->k.N;
-        if ((rc = grow_stage(h, h->obs_map, len))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->obs_map.p, level_map, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
-    }
-    return observe_eval(h, pcof, n_pcof, history_precomputed, Observe{OBS_POPULATIONS, level_map ? n_groups : 0, populations}, out3);
+    return observe_eval(h, pcof, n_pcof, history_precomputed, obs, out3);
 }
 
 
 int qgd_eval_expectations(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed,
                           const double *obs_re, const double *obs_im, int32_t n_obs, double *expect, double *out3)
 {
+    const Observe obs{{false, false, true, nullptr, 0, obs_re, obs_im, n_obs}, expect};
     if (!expect) return fail(h, QGD_ERR_ARGUMENT, "null output array");
-    if (!obs_re || n_obs < 1) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_expectations needs obs_re and n_obs >= 1");
+    int rc;
+    if ((rc = selection_refusals(h, obs.sel, "qgd_eval_expectations"))) return rc;
     ENTER(h, ENTER_KEEPS_GRAPH);
     if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_expectations is single-GPU: this handle has a communicator or a partition");
-    int rc;
     if ((rc = refuse_reuse(h, history_precomputed))) return rc;
-    const size_t len = (size_t)n_obs * h->k.N * h->k.N;
-    if ((rc = grow_stage(h, h->obs_planes, (obs_im ? 2 : 1) * len))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->obs_planes.p, obs_re, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
-    if (obs_im) HIP_TRY(h, hipMemcpyAsync(h->obs_planes.p + len, obs_im, len * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
-    return observe_eval(h, pcof, n_pcof, history_precomputed, Observe{OBS_EXPECTATIONS, 0, expect, n_obs, obs_im != nullptr}, out3);
+    return observe_eval(h, pcof, n_pcof, history_precomputed, obs, out3);
 }
 
 
 // Hermite dense output: the sweep of the three calls above, then the states, populations or expectation
 // values of the interpolant at refine points per step (observe_out: stage derivatives, qgd_k_interp.hip, the same output kernels
-// and transport).  Everything that can refuse the call does so here, before the first launch or upload.
+// and transport).  Everything that can refuse the call does so here, before the first launch or upload.  The selection holds
+// the level map only for populations and the observables only for expectation values: what the kind does not use is not looked at.
 int qgd_eval_dense(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t history_precomputed, int32_t refine, int32_t kind,
                    const double *level_map, int32_t n_groups, const double *obs_re, const double *obs_im, int32_t n_obs,
                    double *out, double *out3)
@@ -636,33 +634,19 @@ int qgd_eval_dense(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t his
         return fail(h, QGD_ERR_ARGUMENT, "refine must be >= 1 and 1 + nsteps * refine fit a 32-bit integer");
     if (kind != QGD_DENSE_STATES && kind != QGD_DENSE_POPULATIONS && kind != QGD_DENSE_EXPECTATIONS)
         return fail(h, QGD_ERR_ARGUMENT, "unknown kind of dense output");
-    if (kind == QGD_DENSE_POPULATIONS && level_map && n_groups < 1) return fail(h, QGD_ERR_ARGUMENT, "a level map needs n_groups >= 1");
-    if (kind == QGD_DENSE_EXPECTATIONS && (!obs_re || n_obs < 1)) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_dense needs obs_re and n_obs >= 1 for expectation values");
+    Observe obs{{kind == QGD_DENSE_STATES, kind == QGD_DENSE_POPULATIONS, kind == QGD_DENSE_EXPECTATIONS}, out, refine};
+    if (obs.sel.pops) { obs.sel.level_map = level_map; obs.sel.n_groups = n_groups; }
+    if (obs.sel.expect) { obs.sel.obs_re = obs_re; obs.sel.obs_im = obs_im; obs.sel.n_obs = n_obs; }
+    int rc;
+    if ((rc = selection_refusals(h, obs.sel, "qgd_eval_dense", " for expectation values"))) return rc;
     ENTER(h, ENTER_KEEPS_GRAPH);
     const qgdk_ctx &k = h->k;
     if (h->comm || h->part_world != 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_dense is single-GPU: this handle has a communicator or a partition");
     if (pcof && !h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before passing pcof");
     if (pcof && n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
     if (!pcof && !h->have_tables && k.n_ops > 0) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
-    int rc;
     if ((rc = refuse_reuse(h, history_precomputed))) return rc;
     if (refine > 1 && (rc = dense_buffers(h, refine))) return rc;      // (QGD_ERR_MEMORY before the sweep is touched)
-    Observe obs{OBS_STATES, 0, out, 0, false, refine};
-    if (kind == QGD_DENSE_POPULATIONS) {
-        obs.kind = OBS_POPULATIONS;
-        if (level_map) {
-            const size_t len = (size_t)n_groups * k.N;
-            if ((rc = grow_stage(h, h->obs_map, len))) return rc;
-            HIP_TRY(h, hipMemcpyAsync(h->obs_map.p, level_map, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
-            obs.n_groups = n_groups;
-        }
-    } else if (kind == QGD_DENSE_EXPECTATIONS) {
-        obs.kind = OBS_EXPECTATIONS; obs.n_obs = n_obs; obs.obs_im = obs_im != nullptr;
-        const size_t len = (size_t)n_obs * k.N * k.N;
-        if ((rc = grow_stage(h, h->obs_planes, (obs_im ? 2 : 1) * len))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->obs_planes.p, obs_re, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
-        if (obs_im) HIP_TRY(h, hipMemcpyAsync(h->obs_planes.p + len, obs_im, len * sizeof(double), hipMemcpyHostToDevice, k.stream));
-    }
     return observe_eval(h, pcof, n_pcof, history_precomputed, obs, out3);
 }
 

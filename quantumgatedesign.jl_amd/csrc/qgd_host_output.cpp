@@ -271,8 +271,9 @@ int observe_out(qgd_handle h, const Observe &obs, int save)
 {
     qgdk_ctx &k = h->k;
     const size_t hstep = (size_t)k.Np * 2 * k.cp;
-    const size_t rows = obs.kind == OBS_STATES ? 2 * (size_t)k.N : obs.kind == OBS_EXPECTATIONS ? (size_t)obs.n_obs
-                      : (obs.n_groups > 0 ? (size_t)obs.n_groups : (size_t)k.N);
+    const OutputSelection &s = obs.sel;
+    const OutputSizes z = output_sizes(s, (size_t)k.N, 1);
+    const size_t rows = z.states + z.pops + z.expect;      // (one of them is selected)
     const bool dense = obs.refine > 1;
     const Span sp = span_of(h, save, 0, dense ? obs.refine : 1);
     if (!sp.count) return QGD_OK;
@@ -289,18 +290,51 @@ int observe_out(qgd_handle h, const Observe &obs, int save)
     }
     if ((rc = grow_stage(h, h->stage_obs, rows * sp.count * k.c))) return rc;
     const double *src = panels + sp.first * hstep;
-    if (obs.kind == OBS_STATES) {
+    if (s.states) {
         K_TRY(h, qgdk_layout(&k, src, (long long)(hstep * sp.stride), 0, h->stage_obs.p, (long long)(sp.count * rows), (long long)rows, 0, 0, (int)sp.count, 1, 0, k.stream, 0));
-    } else if (obs.kind == OBS_EXPECTATIONS) {
+    } else if (s.expect) {
         PhaseTimer t(h, "expectations");
         K_TRY(h, qgdk_expectations(&k, src, (long long)(hstep * sp.stride), h->stage_obs.p, (long long)(sp.count * rows), (long long)rows, (int)sp.count,
-                                   h->obs_planes.p, obs.obs_im ? h->obs_planes.p + (size_t)obs.n_obs * k.N * k.N : nullptr, obs.n_obs, k.stream));
+                                   h->obs_planes.p, s.with_im() ? h->obs_planes.p + z.plane : nullptr, s.n_obs, k.stream));
     } else {
         PhaseTimer t(h, "populations");
         K_TRY(h, qgdk_populations(&k, src, (long long)(hstep * sp.stride), h->stage_obs.p, (long long)(sp.count * rows), (long long)rows, (int)sp.count,
-                                  obs.n_groups > 0 ? h->obs_map.p : nullptr, obs.n_groups, k.stream));
+                                  s.with_map() ? h->obs_map.p : nullptr, s.with_map() ? s.n_groups : 0, k.stream));
     }
     return send_staged(h, h->stage_obs.p, rows, 0, sp, obs.out, rows);
+}
+
+
+// The rules of an OutputSelection (qgd_host.h).  What a call refuses from its selection alone, in front of ENTER (`subject`,
+// `tail`: the caller's wording of the observable message):
+int selection_refusals(qgd_handle h, const OutputSelection &s, const char *subject, const char *tail)
+{
+    if (s.level_map && s.n_groups < 1) return fail(h, QGD_ERR_ARGUMENT, "a level map needs n_groups >= 1");
+    if (s.expect && (!s.obs_re || s.n_obs < 1)) return fail(h, QGD_ERR_ARGUMENT, std::string(subject) + " needs obs_re and n_obs >= 1" + tail);
+    return QGD_OK;
+}
+
+// the doubles of its outputs [2N | n_groups or N | n_obs, sc] and of its uploads [n_groups, N], [N, N, n_obs] once or twice
+OutputSizes output_sizes(const OutputSelection &s, size_t N, size_t sc)
+{
+    OutputSizes z;
+    z.states = s.states ? 2 * N * sc : 0;
+    z.pops = s.pops ? (s.with_map() ? (size_t)s.n_groups : N) * sc : 0;
+    z.expect = s.expect ? (size_t)s.n_obs * sc : 0;
+    z.map = s.with_map() ? (size_t)s.n_groups * N : 0;
+    z.plane = s.expect ? (size_t)s.n_obs * N * N : 0;
+    z.planes = (s.with_im() ? 2 : 1) * z.plane;
+    return z;
+}
+
+// and the uploads themselves: the map, the real planes and the imaginary ones behind them
+int upload_selection(qgd_handle h, const OutputSelection &s, const OutputSizes &z, double *map, double *planes)
+{
+    const struct { double *dst; const double *src; size_t n; } up[] = {
+        {map, s.level_map, z.map}, {planes, s.obs_re, z.plane}, {planes + z.plane, s.obs_im, s.with_im() ? z.plane : 0}};
+    for (const auto &u : up)
+        if (u.n) HIP_TRY(h, hipMemcpyAsync(u.dst, u.src, u.n * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
+    return QGD_OK;
 }
 
 }  // namespace qgdh

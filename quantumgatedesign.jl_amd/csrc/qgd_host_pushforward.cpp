@@ -12,47 +12,30 @@ namespace {
 struct PushforwardCall {
     const double *pcof; int32_t n_pcof, history_precomputed;
     const double *v; int32_t n_vec;
-    double *states_dot, *pop_dot; const double *level_map; int32_t n_groups;
-    double *expect_dot; const double *obs_re, *obs_im; int32_t n_obs;
+    double *states_dot, *pop_dot, *expect_dot;
+    OutputSelection sel;      // the outputs whose array is given
 };
 
-// doubles of one direction of each output as the caller gets it, and of the two uploads
-struct PushforwardSizes { size_t slots, st, po, ex, n_map, n_plane, n_planes; bool with_map, with_im; };
+size_t pushforward_slots(qgd_handle h) { return 1 + (size_t)(h->k.nt - 1) / h->save_every; }
 
-PushforwardSizes pushforward_sizes(qgd_handle h, const PushforwardCall &p)
-{
-    const qgdk_ctx &k = h->k;
-    PushforwardSizes z;
-    const size_t N = k.N;
-    z.slots = 1 + (size_t)(k.nt - 1) / h->save_every;
-    const size_t sc = z.slots * k.c;
-    z.with_map = p.pop_dot && p.level_map; z.with_im = p.expect_dot && p.obs_im;
-    z.st = p.states_dot ? 2 * N * sc : 0;
-    z.po = p.pop_dot ? (z.with_map ? (size_t)p.n_groups : N) * sc : 0;
-    z.ex = p.expect_dot ? (size_t)p.n_obs * sc : 0;
-    z.n_map = z.with_map ? (size_t)p.n_groups * N : 0;
-    z.n_plane = p.expect_dot ? (size_t)p.n_obs * N * N : 0;
-    z.n_planes = (z.with_im ? 2 : 1) * z.n_plane;
-    return z;
-}
-
-// the pool for chunks of up to `cap` directions (the states are staged with their padding columns: cp of them per direction)
-KeyedPlan pushforward_plan(qgd_handle h, const PushforwardSizes &z, size_t cap)
+// the pool for chunks of up to `cap` directions, z: the doubles of one direction of each output as the caller gets it and of the
+// two uploads (the states are staged with their padding columns: cp of them per direction)
+KeyedPlan pushforward_plan(qgd_handle h, const OutputSizes &z, size_t cap)
 {
     const qgdk_ctx &k = h->k;
     const size_t nt = k.nt, np = (size_t)k.n_pcof, NB = (size_t)k.n_ops * 2 * k.m, B = (size_t)k.scan_blocks;
-    const size_t hstep = (size_t)k.Np * 2 * k.cp, st = z.st ? 2 * (size_t)k.N * z.slots * k.cp : 0;
+    const size_t hstep = (size_t)k.Np * 2 * k.cp, st = z.states ? 2 * (size_t)k.N * pushforward_slots(h) * k.cp : 0;
     auto &b = h->pf;
-    return {{nt, np, NB, B, cap, z.st, z.po, z.ex, z.n_map, z.n_planes}, {
+    return {{nt, np, NB, B, cap, z.states, z.pops, z.expect, z.map, z.planes}, {
         {&b.sv, nt * hstep * cap}, {&b.phi, B * hstep * cap}, {&b.bnd, (B + 1) * hstep * cap}, {&b.gvt, qgdk_hvp_gv_len(&k) * cap},
-        {&b.bases, 2 * cap}, {&b.v, np * cap}, {&b.st, st * cap, st != 0}, {&b.po, z.po * cap, z.po != 0}, {&b.ex, z.ex * cap, z.ex != 0},
-        {&b.map, z.n_map, z.n_map != 0}, {&b.planes, z.n_planes, z.n_planes != 0}}};
+        {&b.bases, 2 * cap}, {&b.v, np * cap}, {&b.st, st * cap, st != 0}, {&b.po, z.pops * cap, z.pops != 0}, {&b.ex, z.expect * cap, z.expect != 0},
+        {&b.map, z.map, z.map != 0}, {&b.planes, z.planes, z.planes != 0}}};
 }
 
 // The pool of this call: chunks of `want` directions when that fits, else of as many as the memory budget and the free device
 // memory hold beside the forced gradient's buffers (halving, never below one: QGD_ERR_MEMORY is then the pool's own answer).
 // A pool of the same problem and outputs that is wide enough already is kept.  Returns the chunk's width in `chunk`.
-int pushforward_buffers(qgd_handle h, const PushforwardSizes &z, size_t want, size_t &chunk)
+int pushforward_buffers(qgd_handle h, const OutputSizes &z, size_t want, size_t &chunk)
 {
     qgdk_ctx &k = h->k;
     Pool &pool = h->pools[POOL_PUSHFORWARD];
@@ -87,50 +70,21 @@ int pushforward_buffers(qgd_handle h, const PushforwardSizes &z, size_t want, si
     });
 }
 
-int pushforward_arguments(qgd_handle h, const PushforwardCall &p)
-{
-    if (!p.v) return fail(h, QGD_ERR_ARGUMENT, "null argument");
-    if (p.n_vec < 1) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_pushforward needs at least one direction");
-    if (!p.states_dot && !p.pop_dot && !p.expect_dot) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_pushforward needs at least one of states_dot, pop_dot, expect_dot");
-    if (p.level_map && p.n_groups < 1) return fail(h, QGD_ERR_ARGUMENT, "a level map needs n_groups >= 1");
-    if (p.expect_dot && (!p.obs_re || p.n_obs < 1)) return fail(h, QGD_ERR_ARGUMENT, "expect_dot needs obs_re and n_obs >= 1");
-    return QGD_OK;
-}
-
-int pushforward_refusals(qgd_handle h, const PushforwardCall &p)
-{
-    const qgdk_ctx &k = h->k;
-    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before qgd_eval_pushforward");
-    if (h->part_world != 1 || h->comm) return fail(h, QGD_ERR_STATE, "partitioned handle: the pushforward is single-GPU");
-    if (p.pcof && p.n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
-    if (h->chunks_eff > 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_pushforward needs the whole time grid resident (this handle processes it in windows)");
-    if (k.N > 64) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_pushforward supports N <= 64");
-    if (k.n_ops < 1) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_pushforward needs control operators");
-    if (k.n_ops * 2 * k.m > 64) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_pushforward needs 2 * n_ops * order/2 <= 64 basis directions");
-    if (!p.pcof && !h->have_tables) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
-    return refuse_reuse(h, p.history_precomputed);
-}
-
 int pushforward(qgd_handle h, const PushforwardCall &p)
 {
     qgdk_ctx &k = h->k;
     const int save = h->save_every;
-    const PushforwardSizes z = pushforward_sizes(h, p);
+    const size_t slots = pushforward_slots(h);
+    const OutputSizes z = output_sizes(p.sel, (size_t)k.N, slots * k.c);
     const size_t np = (size_t)k.n_pcof, hstep = (size_t)k.Np * 2 * k.cp, n_vec = (size_t)p.n_vec, B8 = sizeof(double);
     size_t chunk = 0;
     int rc;
     if ((rc = pushforward_buffers(h, z, std::min(n_vec, (size_t)h->pf_chunk_max), chunk))) return rc;
     auto &b = h->pf;
-    const struct { double *dst; const double *src; size_t n; } up[] = {
-        {b.map, p.level_map, z.n_map}, {b.planes, p.obs_re, z.n_plane}, {z.with_im ? b.planes + z.n_plane : nullptr, p.obs_im, z.with_im ? z.n_plane : 0}};
-    for (const auto &u : up)
-        if (u.n) HIP_TRY(h, hipMemcpyAsync(u.dst, u.src, u.n * B8, hipMemcpyHostToDevice, k.stream));
-    // the general two-point forward sweep unless history_precomputed finds one of the same pcof; the stage derivatives; the forced
-    // basis responses unless the stored sweep has them (an earlier pushforward, the setup of qgd_eval_hessian_vec) and their pool
-    // still stands
-    if (!(p.history_precomputed && h->sweep.kind == SWEEP_GENERAL && sweep_reusable(h, p.pcof, p.n_pcof)) &&
-        (rc = run_forward(h, p.pcof, p.n_pcof))) return rc;
-    if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&k)); h->sweep.derivs = true; }
+    if ((rc = upload_selection(h, p.sel, z, b.map, b.planes))) return rc;
+    // the pullbacks' forward sweep and stage derivatives; the forced basis responses unless the stored sweep has them (an earlier
+    // pushforward, the setup of qgd_eval_hessian_vec) and their pool still stands
+    if ((rc = pullback_sweep(h, p.pcof, p.n_pcof, p.history_precomputed))) return rc;
     const bool formed = h->sweep.forced_basis && forced_missing(h) == 0;
     if ((rc = forced_buffers(h, (size_t)k.nt, (size_t)k.scan_blocks))) return rc;
     if (!formed) { PhaseTimer t(h, "forced_basis"); K_TRY(h, qgdk_forced_basis(&k)); h->sweep.forced_basis = true; }
@@ -152,16 +106,16 @@ int pushforward(qgd_handle h, const PushforwardCall &p)
             // takes the c columns of every direction
             qgdk_ctx d = k;
             d.cp = (int)w * k.cp; d.c = d.cp;
-            const size_t rows = 2 * (size_t)k.N, per_dir = rows * z.slots * k.cp;
-            K_TRY(h, qgdk_layout(&d, b.sv, (long long)(hstep * w * save), 0, b.st, (long long)(z.slots * rows), (long long)rows, 0, 0, (int)z.slots, 1, 0, k.stream, 0));
-            HIP_TRY(h, hipMemcpy2DAsync(p.states_dot + j0 * z.st, z.st * B8, b.st, per_dir * B8, z.st * B8, w, hipMemcpyDeviceToHost, k.stream));
+            const size_t rows = 2 * (size_t)k.N, per_dir = rows * slots * k.cp;
+            K_TRY(h, qgdk_layout(&d, b.sv, (long long)(hstep * w * save), 0, b.st, (long long)(slots * rows), (long long)rows, 0, 0, (int)slots, 1, 0, k.stream, 0));
+            HIP_TRY(h, hipMemcpy2DAsync(p.states_dot + j0 * z.states, z.states * B8, b.st, per_dir * B8, z.states * B8, w, hipMemcpyDeviceToHost, k.stream));
         }
         if (p.pop_dot || p.expect_dot) {
             PhaseTimer t(h, "pushforward_outputs", nullptr, slot);
-            K_TRY(h, qgdk_pushforward_outputs(&k, b.sv, (int)w, save, b.po, b.map, p.n_groups, b.ex, b.planes, z.with_im ? b.planes + z.n_plane : nullptr, p.n_obs));
+            K_TRY(h, qgdk_pushforward_outputs(&k, b.sv, (int)w, save, b.po, b.map, p.sel.n_groups, b.ex, b.planes, p.sel.with_im() ? b.planes + z.plane : nullptr, p.sel.n_obs));
         }
-        if (p.pop_dot) HIP_TRY(h, hipMemcpyAsync(p.pop_dot + j0 * z.po, b.po, w * z.po * B8, hipMemcpyDeviceToHost, k.stream));
-        if (p.expect_dot) HIP_TRY(h, hipMemcpyAsync(p.expect_dot + j0 * z.ex, b.ex, w * z.ex * B8, hipMemcpyDeviceToHost, k.stream));
+        if (p.pop_dot) HIP_TRY(h, hipMemcpyAsync(p.pop_dot + j0 * z.pops, b.po, w * z.pops * B8, hipMemcpyDeviceToHost, k.stream));
+        if (p.expect_dot) HIP_TRY(h, hipMemcpyAsync(p.expect_dot + j0 * z.expect, b.ex, w * z.expect * B8, hipMemcpyDeviceToHost, k.stream));
     }
     HIP_TRY(h, hipStreamSynchronize(k.stream));
     return QGD_OK;
@@ -177,11 +131,15 @@ int qgd_eval_pushforward(qgd_handle h, const double *pcof, int32_t n_pcof, int32
                          double *pop_dot, const double *level_map, int32_t n_groups,
                          double *expect_dot, const double *obs_re, const double *obs_im, int32_t n_obs)
 {
-    const PushforwardCall p{pcof, n_pcof, history_precomputed, v, n_vec, states_dot, pop_dot, level_map, n_groups, expect_dot, obs_re, obs_im, n_obs};
+    const PushforwardCall p{pcof, n_pcof, history_precomputed, v, n_vec, states_dot, pop_dot, expect_dot,
+                            {states_dot != nullptr, pop_dot != nullptr, expect_dot != nullptr, level_map, n_groups, obs_re, obs_im, n_obs}};
+    if (!v) return fail(h, QGD_ERR_ARGUMENT, "null argument");
+    if (n_vec < 1) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_pushforward needs at least one direction");
+    if (!states_dot && !pop_dot && !expect_dot) return fail(h, QGD_ERR_ARGUMENT, "qgd_eval_pushforward needs at least one of states_dot, pop_dot, expect_dot");
     int rc;
-    if ((rc = pushforward_arguments(h, p))) return rc;
+    if ((rc = selection_refusals(h, p.sel, "expect_dot"))) return rc;
     ENTER(h);
-    if ((rc = pushforward_refusals(h, p))) return rc;
+    if ((rc = trajectory_refusals(h, "qgd_eval_pushforward", "pushforward", pcof, n_pcof, history_precomputed, true))) return rc;
     return pushforward(h, p);
 }
 

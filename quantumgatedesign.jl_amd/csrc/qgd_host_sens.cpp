@@ -2,7 +2,8 @@
 // (eval_grad_forced.jl:17-194), the exact Hessian, Hessian-vector products (section 4d) and the pullback of
 // trajectory outputs (sections 4g, 4j).  The first three share the forced gradient's buffers, and the two second-order entry points
 // their refusals and their setup; the pullback runs the second-order adjoint's sweep with a forcing of the caller's, and the
-// pullback of the dense output (section 4j) the same sweep behind the transposed interpolation.
+// pullback of the dense output (section 4j) the same sweep behind the transposed interpolation.  qgd_eval_pushforward
+// (qgd_host_pushforward.cpp) takes the pullbacks' refusals behind the prologue and their forward sweep from here.
 #include "qgd_host.h"
 
 using namespace qgdh;
@@ -244,17 +245,21 @@ static int hvp_terminal(qgd_handle h, const double *svN_dev, double *term_dev)
 }
 
 
-// buffers of qgd_eval_pullback for the present grid and basis and the sizes of this call's uploads (doubles; 0: not given)
-static int pullback_buffers(qgd_handle h, size_t n_sbar, size_t n_pbar, size_t n_map, size_t n_ebar, size_t n_planes)
+// The pool of a pullback entry point for the present grid and basis and the sizes of this call's uploads (doubles; 0: not given).
+// Its key: the entry point's `key`, then those five sizes.  Its plan: the entry point's `plan`, F, Y, mu, its `mid`, then the rest
+// of PullbackBufs (qgd_eval_pullback has neither `plan` nor `mid`).
+static int pullback_buffers(qgd_handle h, Pool &pool, qgd_handle_s::PullbackBufs &b, std::vector<size_t> key, const OutputSizes &z, const char *fit,
+                            std::vector<Buf> plan = {}, const std::vector<Buf> &mid = {})
 {
     qgdk_ctx &k = h->k;
     const size_t hist = (size_t)k.nt * k.Np * 2 * k.cp, np = (size_t)k.n_pcof;
-    auto &b = h->pb;
-    return pool_ensure(h, h->pools[POOL_PULLBACK], {{(size_t)k.nt, np, n_sbar, n_pbar, n_map, n_ebar, n_planes}, {
-        {&b.F, hist}, {&b.Y, hist}, {&b.mu, hist}, {&b.gB, np}, {&b.scal, 4}, {&b.sbar, n_sbar, n_sbar != 0}, {&b.pbar, n_pbar, n_pbar != 0},
-        {&b.map, n_map, n_map != 0}, {&b.ebar, n_ebar, n_ebar != 0}, {&b.planes, n_planes, n_planes != 0}}},
-        "the buffers of qgd_eval_pullback do not fit", 0, [&]() -> int {
-        // mu_0 and y_0 are never written; the forcing kernel writes every panel of F on every call
+    key.insert(key.end(), {z.states, z.pops, z.map, z.expect, z.planes});
+    plan.insert(plan.end(), {{&b.F, hist}, {&b.Y, hist}, {&b.mu, hist}});
+    plan.insert(plan.end(), mid.begin(), mid.end());
+    plan.insert(plan.end(), {{&b.gB, np}, {&b.scal, 4}, {&b.sbar, z.states, z.states != 0}, {&b.pbar, z.pops, z.pops != 0},
+                             {&b.map, z.map, z.map != 0}, {&b.ebar, z.expect, z.expect != 0}, {&b.planes, z.planes, z.planes != 0}});
+    return pool_ensure(h, pool, {key, plan}, fit, 0, [&]() -> int {
+        // mu_0 and y_0 are never written; the kernels write every panel and entry of the other work buffers on every call
         HIP_TRY(h, hipMemsetAsync(b.mu, 0, hist * sizeof(double), k.stream));
         HIP_TRY(h, hipMemsetAsync(b.Y, 0, hist * sizeof(double), k.stream));
         HIP_TRY(h, hipMemsetAsync(b.scal, 0, 4 * sizeof(double), k.stream));
@@ -274,14 +279,45 @@ static qgdk_ctx adjoint_context(const qgdk_ctx &k, double *F, double *Y, double 
 }
 
 
-// The arguments of a pullback entry point (`name`: for the messages), what both entry points refuse before anything is launched
-// (from their arguments alone, in front of ENTER, and of the handle's state behind it), their forward sweep, and the grid-point
-// pullback itself with slot k at time point k * save.
+namespace qgdh {
+
+// what the pullbacks and qgd_eval_pushforward refuse once they have entered (`name`: the entry point, `what`: "pullback" or
+// "pushforward", for the messages; basis_bound: the forced scan's bound on the basis directions applies)
+int trajectory_refusals(qgd_handle h, const std::string &name, const char *what, const double *pcof, int n_pcof, int history_precomputed, bool basis_bound)
+{
+    const qgdk_ctx &k = h->k;
+    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before " + name);
+    if (h->part_world != 1 || h->comm) return fail(h, QGD_ERR_STATE, std::string("partitioned handle: the ") + what + " is single-GPU");
+    if (pcof && n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
+    if (h->chunks_eff > 1) return fail(h, QGD_ERR_UNSUPPORTED, name + " needs the whole time grid resident (this handle processes it in windows)");
+    if (k.N > 64) return fail(h, QGD_ERR_UNSUPPORTED, name + " supports N <= 64");
+    if (k.n_ops < 1) return fail(h, QGD_ERR_UNSUPPORTED, name + " needs control operators");
+    if (basis_bound && k.n_ops * 2 * k.m > 64) return fail(h, QGD_ERR_UNSUPPORTED, name + " needs 2 * n_ops * order/2 <= 64 basis directions");
+    if (!pcof && !h->have_tables) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
+    return refuse_reuse(h, history_precomputed);
+}
+
+// their forward sweep: the general two-point one unless history_precomputed finds one of the same pcof, and the stage derivatives
+int pullback_sweep(qgd_handle h, const double *pcof, int n_pcof, int history_precomputed)
+{
+    int rc;
+    if (!(history_precomputed && h->sweep.kind == SWEEP_GENERAL && sweep_reusable(h, pcof, n_pcof)) && (rc = run_forward(h, pcof, n_pcof))) return rc;
+    if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&h->k)); h->sweep.derivs = true; }
+    return QGD_OK;
+}
+
+}  // namespace qgdh
+
+
+// The arguments of a pullback entry point (`name`: for the messages; sel: the outputs whose cotangent is given), what both entry
+// points refuse from them alone, in front of ENTER, and the steps they share around their forcing kernels: the uploads and the
+// forward sweep (the pool `b` is ensured), and the adjoint sweep with the forcing in b.F, the gradient kernels with mu in place
+// of lambda -- the dense pullback then accumulates its explicit part -- the status and the download.
 struct PullbackCall {
     const char *name;
     const double *pcof; int32_t n_pcof, history_precomputed;
-    const double *states_bar, *pop_bar, *level_map; int32_t n_groups;
-    const double *expect_bar, *obs_re, *obs_im; int32_t n_obs;
+    const double *states_bar, *pop_bar, *expect_bar;
+    OutputSelection sel;
     double *grad;
 };
 
@@ -289,61 +325,49 @@ static int pullback_arguments(qgd_handle h, const PullbackCall &p)
 {
     if (!p.grad) return fail(h, QGD_ERR_ARGUMENT, "null argument");
     if (!p.states_bar && !p.pop_bar && !p.expect_bar) return fail(h, QGD_ERR_ARGUMENT, std::string(p.name) + " needs at least one of states_bar, pop_bar, expect_bar");
-    if (p.level_map && p.n_groups < 1) return fail(h, QGD_ERR_ARGUMENT, "a level map needs n_groups >= 1");
-    if (p.expect_bar && (!p.obs_re || p.n_obs < 1)) return fail(h, QGD_ERR_ARGUMENT, "expect_bar needs obs_re and n_obs >= 1");
-    return QGD_OK;
+    return selection_refusals(h, p.sel, "expect_bar");
 }
 
-static int pullback_refusals(qgd_handle h, const PullbackCall &p)
+static int pullback_begin(qgd_handle h, const PullbackCall &p, const OutputSizes &z, const qgd_handle_s::PullbackBufs &b)
 {
-    const std::string name = p.name;
-    const qgdk_ctx &k = h->k;
-    if (!h->have_basis) return fail(h, QGD_ERR_STATE, "qgd_set_control_basis must be called before " + name);
-    if (h->part_world != 1 || h->comm) return fail(h, QGD_ERR_STATE, "partitioned handle: the pullback is single-GPU");
-    if (p.pcof && p.n_pcof != k.n_pcof) return fail(h, QGD_ERR_ARGUMENT, "length of pcof does not match the control basis");
-    if (h->chunks_eff > 1) return fail(h, QGD_ERR_UNSUPPORTED, name + " needs the whole time grid resident (this handle processes it in windows)");
-    if (k.N > 64) return fail(h, QGD_ERR_UNSUPPORTED, name + " supports N <= 64");
-    if (k.n_ops < 1) return fail(h, QGD_ERR_UNSUPPORTED, name + " needs control operators");
-    if (!p.pcof && !h->have_tables) return fail(h, QGD_ERR_STATE, "no control tables: call qgd_set_control_tables or pass pcof");
-    return refuse_reuse(h, p.history_precomputed);
+    const struct { double *dst; const double *src; size_t n; } up[] = {{b.sbar, p.states_bar, z.states}, {b.pbar, p.pop_bar, z.pops}, {b.ebar, p.expect_bar, z.expect}};
+    for (const auto &u : up)
+        if (u.n) HIP_TRY(h, hipMemcpyAsync(u.dst, u.src, u.n * sizeof(double), hipMemcpyHostToDevice, h->k.stream));
+    const int rc = upload_selection(h, p.sel, z, b.map, b.planes);
+    return rc ? rc : pullback_sweep(h, p.pcof, p.n_pcof, p.history_precomputed);
 }
 
-// the general two-point forward sweep unless history_precomputed finds one of the same pcof, and the stage derivatives
-static int pullback_sweep(qgd_handle h, const PullbackCall &p)
+static int pullback_end(qgd_handle h, const qgd_handle_s::PullbackBufs &b, double *grad, const qgd_handle_s::DensePullbackBufs *dense = nullptr)
 {
+    qgdk_ctx &k = h->k;
+    const qgdk_ctx a = adjoint_context(k, b.F, b.Y, b.mu, b.gB, b.scal);
+    { PhaseTimer t(h, dense ? "dense_pullback_adjoint" : "pullback_adjoint"); K_TRY(h, qgdk_hvp_adjoint(&a)); }
+    { PhaseTimer t(h, dense ? "dense_pullback_gradient" : "pullback_gradient"); K_TRY(h, qgdk_gradient(&a)); }      // gB = the implicit part
+    if (dense) {   // gB += the explicit part: k_contract over the planes of the column groups of the call's own sigma
+        qgdk_ctx e = a;
+        e.sigma = dense->sigma; e.cpart = dense->cpart; e.dense_gemm = 0; e.grad_accumulate = 1;
+        PhaseTimer t(h, "dense_pullback_explicit");
+        K_TRY(h, qgdk_contract(&e));
+    }
     int rc;
-    if (!(p.history_precomputed && h->sweep.kind == SWEEP_GENERAL && sweep_reusable(h, p.pcof, p.n_pcof)) &&
-        (rc = run_forward(h, p.pcof, p.n_pcof))) return rc;
-    if (!h->sweep.derivs) { PhaseTimer t(h, "derivs"); K_TRY(h, qgdk_derivs(&h->k)); h->sweep.derivs = true; }
+    if ((rc = check_status(h))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(grad, b.gB, (size_t)k.n_pcof * sizeof(double), hipMemcpyDeviceToHost, k.stream));
+    HIP_TRY(h, hipStreamSynchronize(k.stream));
     return QGD_OK;
 }
 
+// the grid-point pullback, slot k at time point k * save
 static int pullback_grid(qgd_handle h, const PullbackCall &p, int save)
 {
     qgdk_ctx &k = h->k;
-    const size_t np = (size_t)k.n_pcof, N = k.N, sc = (size_t)(1 + (k.nt - 1) / save) * k.c;      // sc: slots x columns
-    const bool with_map = p.pop_bar && p.level_map, with_im = p.expect_bar && p.obs_im;
-    const size_t n_sbar = p.states_bar ? 2 * N * sc : 0, n_pbar = p.pop_bar ? (with_map ? (size_t)p.n_groups : N) * sc : 0;
-    const size_t n_map = with_map ? (size_t)p.n_groups * N : 0, n_ebar = p.expect_bar ? (size_t)p.n_obs * sc : 0;
-    const size_t n_plane = p.expect_bar ? (size_t)p.n_obs * N * N : 0;
+    const OutputSizes z = output_sizes(p.sel, (size_t)k.N, (size_t)(1 + (k.nt - 1) / save) * k.c);
+    auto &b = h->pb;
     int rc;
-    if ((rc = pullback_buffers(h, n_sbar, n_pbar, n_map, n_ebar, (with_im ? 2 : 1) * n_plane))) return rc;
-    const auto &b = h->pb;
-    const struct { double *dst; const double *src; size_t n; } up[] = {
-        {b.sbar, p.states_bar, n_sbar}, {b.pbar, p.pop_bar, n_pbar}, {b.map, p.level_map, n_map}, {b.ebar, p.expect_bar, n_ebar},
-        {b.planes, p.obs_re, n_plane}, {with_im ? b.planes + n_plane : nullptr, p.obs_im, with_im ? n_plane : 0}};
-    for (const auto &u : up)
-        if (u.n) HIP_TRY(h, hipMemcpyAsync(u.dst, u.src, u.n * sizeof(double), hipMemcpyHostToDevice, k.stream));
-    if ((rc = pullback_sweep(h, p))) return rc;
+    if ((rc = pullback_buffers(h, h->pools[POOL_PULLBACK], b, {(size_t)k.nt, (size_t)k.n_pcof}, z, "the buffers of qgd_eval_pullback do not fit"))) return rc;
+    if ((rc = pullback_begin(h, p, z, b))) return rc;
     { PhaseTimer t(h, "pullback_forcing");
-      K_TRY(h, qgdk_pullback_forcing(&k, b.F, save, b.sbar, b.pbar, b.map, p.n_groups, b.ebar, b.planes, with_im ? b.planes + n_plane : nullptr, p.n_obs)); }
-    const qgdk_ctx a = adjoint_context(k, b.F, b.Y, b.mu, b.gB, b.scal);
-    { PhaseTimer t(h, "pullback_adjoint"); K_TRY(h, qgdk_hvp_adjoint(&a)); }
-    { PhaseTimer t(h, "pullback_gradient"); K_TRY(h, qgdk_gradient(&a)); }
-    if ((rc = check_status(h))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(p.grad, b.gB, np * sizeof(double), hipMemcpyDeviceToHost, k.stream));
-    HIP_TRY(h, hipStreamSynchronize(k.stream));
-    return QGD_OK;
+      K_TRY(h, qgdk_pullback_forcing(&k, b.F, save, b.sbar, b.pbar, b.map, p.sel.n_groups, b.ebar, b.planes, p.sel.with_im() ? b.planes + z.plane : nullptr, p.sel.n_obs)); }
+    return pullback_end(h, b, p.grad);
 }
 
 
@@ -489,11 +513,12 @@ int qgd_eval_pullback(qgd_handle h, const double *pcof, int32_t n_pcof, int32_t 
                       const double *expect_bar, const double *obs_re, const double *obs_im, int32_t n_obs,
                       double *grad)
 {
-    const PullbackCall p{"qgd_eval_pullback", pcof, n_pcof, history_precomputed, states_bar, pop_bar, level_map, n_groups, expect_bar, obs_re, obs_im, n_obs, grad};
+    const PullbackCall p{"qgd_eval_pullback", pcof, n_pcof, history_precomputed, states_bar, pop_bar, expect_bar,
+                         {states_bar != nullptr, pop_bar != nullptr, expect_bar != nullptr, level_map, n_groups, obs_re, obs_im, n_obs}, grad};
     int rc;
     if ((rc = pullback_arguments(h, p))) return rc;
     ENTER(h);
-    if ((rc = pullback_refusals(h, p))) return rc;
+    if ((rc = trajectory_refusals(h, p.name, "pullback", pcof, n_pcof, history_precomputed, false))) return rc;
     return pullback_grid(h, p, h->save_every);
 }
 
@@ -510,68 +535,38 @@ int qgd_eval_dense_pullback(qgd_handle h, const double *pcof, int32_t n_pcof, in
                             const double *expect_bar, const double *obs_re, const double *obs_im, int32_t n_obs,
                             double *grad)
 {
-    const PullbackCall p{"qgd_eval_dense_pullback", pcof, n_pcof, history_precomputed, states_bar, pop_bar, level_map, n_groups, expect_bar, obs_re, obs_im, n_obs, grad};
+    const PullbackCall p{"qgd_eval_dense_pullback", pcof, n_pcof, history_precomputed, states_bar, pop_bar, expect_bar,
+                         {states_bar != nullptr, pop_bar != nullptr, expect_bar != nullptr, level_map, n_groups, obs_re, obs_im, n_obs}, grad};
     if (grad && (refine < 1 || (h && (long long)h->nsteps * refine + 1 > 0x7fffffffLL)))
         return fail(h, QGD_ERR_ARGUMENT, "refine must be >= 1 and 1 + nsteps * refine fit a 32-bit integer");
     int rc;
     if ((rc = pullback_arguments(h, p))) return rc;
     ENTER(h);
-    if ((rc = pullback_refusals(h, p))) return rc;
+    if ((rc = trajectory_refusals(h, p.name, "pullback", pcof, n_pcof, history_precomputed, false))) return rc;
     if (refine == 1) return pullback_grid(h, p, 1);      // (whatever qgd_set_save_every says: the dense output returns every point)
     qgdk_ctx &k = h->k;
     if (k.m > 8) return fail(h, QGD_ERR_UNSUPPORTED, "qgd_eval_dense_pullback with refine > 1 supports order <= 16 (the interpolation kernels cover order/2 <= 8)");
-    const size_t nt = k.nt, pts = 1 + (nt - 1) * (size_t)refine, np = (size_t)k.n_pcof, N = k.N, sc = pts * k.c, m = k.m;
-    const size_t hstep = (size_t)k.Np * 2 * k.cp, hist = nt * hstep;
-    const bool with_map = pop_bar && level_map, with_im = expect_bar && obs_im;
-    const size_t n_sbar = states_bar ? 2 * N * sc : 0, n_pbar = pop_bar ? (with_map ? (size_t)n_groups : N) * sc : 0;
-    const size_t n_map = with_map ? (size_t)n_groups * N : 0, n_ebar = expect_bar ? (size_t)n_obs * sc : 0;
-    const size_t n_plane = expect_bar ? (size_t)n_obs * N * N : 0, n_planes = (with_im ? 2 : 1) * n_plane;
+    const size_t nt = k.nt, pts = 1 + (nt - 1) * (size_t)refine, np = (size_t)k.n_pcof, m = k.m, hstep = (size_t)k.Np * 2 * k.cp;
+    const OutputSizes z = output_sizes(p.sel, (size_t)k.N, pts * k.c);
     // buffers: the dense panels and the weight table under POOL_DENSE's key, the rest in a pool of this call's own
     if ((rc = dense_buffers(h, refine))) return rc;
     size_t dt_bits = 0;
     memcpy(&dt_bits, &k.dt, sizeof(double) < sizeof(size_t) ? sizeof(double) : sizeof(size_t));
     auto &b = h->dpb;
-    rc = pool_ensure(h, h->pools[POOL_DENSE_PULLBACK], {{nt, (size_t)refine, np, m, dt_bits, n_sbar, n_pbar, n_map, n_ebar, n_planes}, {
-        {&b.G, pts * hstep}, {&b.gbar, nt * (m + 1) * hstep}, {&b.F, hist}, {&b.Y, hist}, {&b.mu, hist},
-        {&b.sigma, (size_t)(k.cp / 8) * nt * k.n_ops * m * 2}, {&b.cpart, ((nt + 7) / 8) * np}, {&b.gB, np}, {&b.scal, 4},
-        {&b.sbar, n_sbar, n_sbar != 0}, {&b.pbar, n_pbar, n_pbar != 0}, {&b.map, n_map, n_map != 0}, {&b.ebar, n_ebar, n_ebar != 0},
-        {&b.planes, n_planes, n_planes != 0}}},
-        "the buffers of qgd_eval_dense_pullback do not fit", 0, [&]() -> int {
-        // mu_0 and y_0 are never written; the kernels write every panel of G, gbar and F and every entry of sigma on every call
-        HIP_TRY(h, hipMemsetAsync(b.mu, 0, hist * sizeof(double), k.stream));
-        HIP_TRY(h, hipMemsetAsync(b.Y, 0, hist * sizeof(double), k.stream));
-        HIP_TRY(h, hipMemsetAsync(b.scal, 0, 4 * sizeof(double), k.stream));
-        return QGD_OK;
-    });
-    if (rc) return rc;
-    const struct { double *dst; const double *src; size_t n; } up[] = {
-        {b.sbar, states_bar, n_sbar}, {b.pbar, pop_bar, n_pbar}, {b.map, level_map, n_map}, {b.ebar, expect_bar, n_ebar},
-        {b.planes, obs_re, n_plane}, {with_im ? b.planes + n_plane : nullptr, obs_im, with_im ? n_plane : 0}};
-    for (const auto &u : up)
-        if (u.n) HIP_TRY(h, hipMemcpyAsync(u.dst, u.src, u.n * sizeof(double), hipMemcpyHostToDevice, k.stream));
-    if ((rc = pullback_sweep(h, p))) return rc;
+    if ((rc = pullback_buffers(h, h->pools[POOL_DENSE_PULLBACK], b, {nt, (size_t)refine, np, m, dt_bits}, z, "the buffers of qgd_eval_dense_pullback do not fit",
+                               {{&b.G, pts * hstep}, {&b.gbar, nt * (m + 1) * hstep}},
+                               {{&b.sigma, (size_t)(k.cp / 8) * nt * k.n_ops * m * 2}, {&b.cpart, ((nt + 7) / 8) * np}}))) return rc;
+    if ((rc = pullback_begin(h, p, z, b))) return rc;
     { PhaseTimer t(h, "dense_pullback_interp"); K_TRY(h, qgdk_interp(&k, k.hist, k.dpsi, h->dense_panels, refine, h->dense_w, k.stream)); }
     {   // the forcing kernel takes its history and its point count from the context: the dense panels, every slot addressed
         qgdk_ctx d = k;
         d.hist = h->dense_panels; d.nt = (int)pts;
         PhaseTimer t(h, "dense_pullback_forcing");
-        K_TRY(h, qgdk_pullback_forcing(&d, b.G, 1, b.sbar, b.pbar, b.map, n_groups, b.ebar, b.planes, with_im ? b.planes + n_plane : nullptr, n_obs));
+        K_TRY(h, qgdk_pullback_forcing(&d, b.G, 1, b.sbar, b.pbar, b.map, n_groups, b.ebar, b.planes, p.sel.with_im() ? b.planes + z.plane : nullptr, n_obs));
     }
     { PhaseTimer t(h, "dense_pullback_transpose"); K_TRY(h, qgdk_interp_transpose(&k, b.G, b.gbar, refine, h->dense_w)); }
     { PhaseTimer t(h, "dense_pullback_sweep"); K_TRY(h, qgdk_dense_pullback_sweep(&k, b.gbar, b.F, b.sigma)); }
-    const qgdk_ctx a = adjoint_context(k, b.F, b.Y, b.mu, b.gB, b.scal);
-    { PhaseTimer t(h, "dense_pullback_adjoint"); K_TRY(h, qgdk_hvp_adjoint(&a)); }
-    { PhaseTimer t(h, "dense_pullback_gradient"); K_TRY(h, qgdk_gradient(&a)); }      // gB = the implicit part
-    {   // gB += the explicit part: k_contract over the planes of the column groups of the call's own sigma
-        qgdk_ctx e = a;
-        e.sigma = b.sigma; e.cpart = b.cpart; e.dense_gemm = 0; e.grad_accumulate = 1;
-        PhaseTimer t(h, "dense_pullback_explicit");
-        K_TRY(h, qgdk_contract(&e));
-    }
-    if ((rc = check_status(h))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(grad, b.gB, np * sizeof(double), hipMemcpyDeviceToHost, k.stream));
-    HIP_TRY(h, hipStreamSynchronize(k.stream));
-    return QGD_OK;
+    return pullback_end(h, b, grad, &b);
 }
 
 }  // extern "C"
