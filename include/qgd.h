@@ -564,5 +564,7 @@ int qgd_get_operator_path(qgd_handle h, int32_t *out3);
 
 /* directional derivatives J v of the states, populations and expectation values */
 #include "qgd_pushforward.h"
+/* one coefficient vector over the members of an ensemble side by side, reduced on the device */
+#include "qgd_ensemble.h"
 
 #endif

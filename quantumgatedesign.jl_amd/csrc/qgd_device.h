@@ -204,6 +204,12 @@ typedef struct { const double *pcofs; double *tab, *Rg, *Linv, *psi, *lam, *cpar
 void qgdk_tiny_batch_layout(const qgdk_ctx *c, int n_pcof, size_t *tab, size_t *mat, size_t *cpart);
 int qgdk_tiny_eval_batch(const qgdk_ctx *c, const qgdk_tiny_batch *b, int members, int n_pcof, int gradient);
 int qgdk_contract_rows_batch(const qgdk_ctx *c, const qgdk_tiny_batch *b, int members, int n_pcof, int rows);
+// an ensemble (qgd_eval_ensemble): one coefficient vector over the members' operator planes ops[members][qgdk_tiny_ensemble_planes],
+// on the batch's per-member arrays; then the weighted sums of the chunk's result rows into acc[n_pcof + 2] = (grad | cost |
+// guard), k ascending from 0.0 (first) or from what acc holds, and the rows' tails into tails[members][5]
+size_t qgdk_tiny_ensemble_planes(const qgdk_ctx *c);
+int qgdk_tiny_eval_ensemble(const qgdk_ctx *c, const qgdk_tiny_batch *b, const double *ops, const double *pcof_host, int members, int n_pcof, int gradient);
+int qgdk_ensemble_reduce(const qgdk_ctx *c, const double *rows, const double *weights, double *acc, double *tails, int members, int n_pcof, int first, int gradient);
 int qgdk_mirror_scalars(const qgdk_ctx *c);      // result mirror of an evaluation without a gradient: [scal | status | sequence number]
 size_t qgdk_lds_needed(int Np, int m, int n_ops);
 int qgdk_sparse_supported(int Np, int m, int n_ops, int Z);

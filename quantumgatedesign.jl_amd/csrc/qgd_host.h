@@ -1,9 +1,10 @@
-// qgd_host.h -- what the seven host-side translation units of the C ABI share (include/qgd.h): the handle, the error and
+// qgd_host.h -- what the eight host-side translation units of the C ABI share (include/qgd.h): the handle, the error and
 // launch macros, the phase timer and the internal entry points of each unit.
 //   qgd_host_alloc.cpp    handles: creation, validation (SchrodingerProb.jl:73-154), the time grid and its windows, setters
 //   qgd_host_eval.cpp     one evaluation: forward / adjoint phases, result transport, the evaluation entry points
 //   qgd_host_sens.cpp     sensitivities of the state to the parameters: the forced gradient, the exact Hessian, Hessian-vector products, pullbacks (grid points and dense output); the refusals and the sweep they share with the pushforward
 //   qgd_host_pushforward.cpp  directional derivatives of the trajectory outputs (include/qgd_pushforward.h)
+//   qgd_host_ensemble.cpp  one pcof over the members of an ensemble side by side, reduced on the device (include/qgd_ensemble.h)
 //   qgd_host_output.cpp   reference-layout output arrays of a resident or windowed grid: the copy stream, staging, the one transport; the rules of an OutputSelection
 //   qgd_host_windows.cpp  time grids in bounded memory: window entry, the windowed forward and adjoint passes
 //   qgd_host_comm.cpp     several GPUs: the RCCL binding, the collective evaluation and its failure mode
@@ -88,7 +89,8 @@ struct StoredSweep {
 // pool_release frees them, writes NULL (and length 0) into every slot and clears the key; pool_missing: the bytes pool_ensure
 // would allocate for a (key, plan) pair.  The other functions are in qgd_host_alloc.cpp.
 #define QGD_BATCH_CHUNK_MAX 1024      // members of a batch that share one set of launches (qgd_eval_batch)
-#define QGD_PUSHFORWARD_CHUNK_MAX 4096     // directions of a pushforward that ride along in one forced scan (qgd_eval_pushforward) ...
+#define QGD_ENSEMBLE_ACC 72           // doubles of the accumulator row of qgd_eval_ensemble: the small path's 64 coefficients at most, cost, guard
+#define QGD_PUSHFORWARD_CHUNK_MAX 4096    // directions of a pushforward that ride along in one forced scan (qgd_eval_pushforward) ...
 #define QGD_PUSHFORWARD_CHUNK_DEFAULT 256  // ... and without QGD_PUSHFORWARD_CHUNK (cnot3's 180 in one scan: 812 MB of tangent history; 13.2 ms against 16.8 in chunks of 32)
 struct Buf { double **slot; size_t count; bool on = true; };
 inline size_t plan_bytes(const std::vector<Buf> &plan) { size_t n = 0; for (const Buf &b : plan) n += b.on ? b.count : 0; return n * sizeof(double); }
@@ -100,7 +102,7 @@ struct Pool {
 };
 struct KeyedPlan { std::vector<size_t> key; std::vector<Buf> plan; };
 inline size_t pool_missing(const Pool &pool, const KeyedPlan &p) { return pool.key == p.key ? 0 : plan_bytes(p.plan); }
-enum { POOL_FORCED, POOL_HESS, POOL_HVP, POOL_PULLBACK, POOL_DENSE, POOL_BATCH, POOL_DENSE_PULLBACK, POOL_PUSHFORWARD, N_SENS_POOLS, POOL_FORCING = N_SENS_POOLS, POOL_STAGE, N_POOLS };
+enum { POOL_FORCED, POOL_HESS, POOL_HVP, POOL_PULLBACK, POOL_DENSE, POOL_BATCH, POOL_DENSE_PULLBACK, POOL_PUSHFORWARD, POOL_ENSEMBLE, N_SENS_POOLS, POOL_FORCING = N_SENS_POOLS, POOL_STAGE, N_POOLS };
 
 struct qgd_handle_s {
     qgdk_ctx k{};
@@ -122,6 +124,7 @@ struct qgd_handle_s {
     //   POOL_BATCH     qgd_eval_batch on the small-problem path (bt): the arrays of a chunk's members; key (chunk members, nt, m, n_ops, n_pcof)
     //   POOL_DENSE_PULLBACK  qgd_eval_dense_pullback (dpb); key (time points, refine, n_pcof, m, bits of dt, the lengths of the five uploads)
     //   POOL_PUSHFORWARD  qgd_eval_pushforward (pf); key (nt, n_pcof, basis directions, scan blocks, directions of a chunk, the lengths of the three staged outputs and the two uploads)
+    //   POOL_ENSEMBLE  qgd_set_ensemble (ens): the members' operator planes and weights, the accumulator row and the rows' tails of qgd_eval_ensemble; key (members, N, n_ops)
     //   POOL_FORCING   qgd_eval_forward with a user forcing (k.ff_*, fsc_forcing); key (nt, scan blocks)
     //   POOL_STAGE     the staging buffers of the reference-layout outputs: no key, each made or grown on first need
     Pool pools[N_POOLS];
@@ -174,6 +177,11 @@ struct qgd_handle_s {
     size_t batch_host_len = 0;
     int batch_chunk_max = (getenv("QGD_BATCH_CHUNK") && atoi(getenv("QGD_BATCH_CHUNK")) >= 1) ? std::min(atoi(getenv("QGD_BATCH_CHUNK")), QGD_BATCH_CHUNK_MAX) : QGD_BATCH_CHUNK_MAX;
     bool batch_path = false;
+    // qgd_set_ensemble / qgd_eval_ensemble: the members' operator planes [members][(2 + 2 n_ops) Np Np] in
+    // the layout of k.ops, their weights, the accumulator row [QGD_ENSEMBLE_ACC] = (grad | cost | guard) that stays on the device
+    // between the chunks of one call, and the tails [members][5] of the members' result rows.  ops == NULL: no ensemble is set
+    // (the pool is released with the sensitivity pools).  The per-member arrays of a chunk are POOL_BATCH's.
+    struct EnsembleBufs { double *ops = nullptr, *w = nullptr, *acc = nullptr, *tails = nullptr; int members = 0; } ens;
     std::vector<double> dense_w_host;
     bool have_basis = false, have_tables = false;
     StoredSweep sweep;
@@ -320,6 +328,13 @@ inline void pack_panel(double *panel, int PW, const double *a, int N, int c, siz
         const size_t o = panel_index(i, col, PW);
         panel[o] = a[i + ld * col]; panel[o + 8] = a[N + i + ld * col];
     }
+}
+
+// An operator [N x N] (column-major) into plane `slot` of the padded column-major planes [Np x Np] of qgdk_ctx::ops (zeroed by
+// the caller): qgd_create's own planes and those of every member of qgd_set_ensemble.
+inline void pack_plane(double *planes, size_t slot, size_t Np, int N, const double *A)
+{
+    for (int j = 0; j < N; j++) for (int i = 0; i < N; i++) planes[slot * Np * Np + i + Np * j] = A[i + (size_t)N * j];
 }
 
 inline void unpack_panel(double *a, size_t ld, const double *panel, int PW, int N, int c)
@@ -512,6 +527,7 @@ bool tiny_applies(qgd_handle h, const double *pcof, int n_pcof);
 int tiny_evaluate(qgd_handle h, const double *pcof, int n_pcof, bool gradient, double *grad, double *out3);
 int check_status(qgd_handle h);
 int fetch_results(qgd_handle h, double *grad, double *out3, const double *src = nullptr);
+int batch_buffers(qgd_handle h, int n_pcof, int *members);
 
 // qgd_host_windows.cpp
 int enter_window(qgd_handle h, const double *pcof, int r, bool with_start_state);

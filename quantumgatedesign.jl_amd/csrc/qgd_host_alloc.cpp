@@ -374,9 +374,7 @@ int qgd_create(const qgd_problem_desc *d, qgd_handle *out)
     const size_t Np = k.Np, pl = Np * Np, PWc = 2 * k.cp;
     // operators: column-major padded planes K_sys, S_sys, Asym_1, Sym_1, ...
     std::vector<double> ops((2 + 2 * (size_t)n_ops) * pl, 0.0);
-    auto put = [&](size_t slot, const double *A) {
-        for (int j = 0; j < N; j++) for (int i = 0; i < N; i++) ops[slot * pl + i + Np * j] = A[i + (size_t)N * j];
-    };
+    auto put = [&](size_t slot, const double *A) { pack_plane(ops.data(), slot, Np, N, A); };
     put(0, d->system_asym); put(1, d->system_sym);
     for (int o = 0; o < n_ops; o++) { put(2 + 2 * o, d->asym_ops + (size_t)o * N * N); put(3 + 2 * o, d->sym_ops + (size_t)o * N * N); }
     CREATE_RC(dev_alloc(h, h->static_bufs, &k.ops, ops.size()));

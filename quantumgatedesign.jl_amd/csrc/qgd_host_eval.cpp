@@ -438,10 +438,12 @@ static int forward_forced(qgd_handle h, const double *pcof, int32_t n_pcof, cons
 }
 
 
+}  // extern "C"
+
 // The device arrays of a batch chunk (POOL_BATCH) and its pinned staging buffer.  *members: in, the chunk the call would like;
 // out, the chunk it gets -- what the memory budget and the free device memory hold, never below one member.  A pool made for a
-// larger chunk of the same problem is kept as it is.
-static int batch_buffers(qgd_handle h, int n_pcof, int *members)
+// larger chunk of the same problem is kept as it is.  (qgd_eval_ensemble takes its per-member arrays from here too.)
+int qgdh::batch_buffers(qgd_handle h, int n_pcof, int *members)
 {
     const qgdk_ctx &k = h->k;
     Pool &pool = h->pools[POOL_BATCH];
@@ -477,6 +479,8 @@ static int batch_buffers(qgd_handle h, int n_pcof, int *members)
     *members = (int)std::min<size_t>(Kc, (size_t)*members);
     return QGD_OK;
 }
+
+extern "C" {
 
 
 // Many coefficient vectors of one problem in one call.  On the small-problem path the members of a

@@ -514,6 +514,50 @@ __global__ __launch_bounds__(1024) void k_contract_sum(const double *__restrict_
     }
 }
 
+// The weighted sums of an ensemble (qgd_eval_ensemble) over the result rows of one chunk,
+// rows[members][n_pcof + 5] as the batched k_contract_sum leaves them: ONE workgroup, lane e < n_pcof owns gradient entry e,
+// lanes n_pcof and n_pcof + 1 own cost and guard (a forward-only call runs those two alone).  The statement is ensemble_reduce
+// of ensemble.py, operation for operation, every operation rounded on its own:
+//   cost_k = 1.0 - (a_k a_k + b_k b_k) / double(n_ess n_ess) for :Infidelity, a_k for every other cost type; guard_k = row[n_pcof + 2]
+//   acc = acc + w_k x_k, k ascending, from the double 0.0 (first chunk of a call) or from acc[] (the chunks before this one)
+// The compiler's default contraction would fuse the product into the sum (the _rn intrinsics do not keep it from that
+// here): it is switched off for these two bodies, and the division is the IEEE one.  The loads of four members are issued
+// ahead of the add chain, which stays in order.  No atomics, nothing waits for another workgroup.  Behind the sums the
+// workgroup packs the rows' tails (three scalars, singular flag, status word) into tails[members][5]: what a call that wants no
+// member gradients downloads.
+struct EnsembleReduce { const double *rows, *w; double *acc, *tails; int members, n_pcof, first, gradient, infidelity, n_ess; };
+__device__ __forceinline__ double ensemble_entry(const double *__restrict__ row, const int e, const int n_pcof, const int infidelity, const double d)
+{
+    #pragma clang fp contract(off)
+    if (e < n_pcof) return row[e];
+    if (e > n_pcof) return row[n_pcof + 2];
+    const double a = row[n_pcof], b = row[n_pcof + 1];
+    return infidelity ? 1.0 - (a * a + b * b) / d : a;
+}
+__global__ __launch_bounds__(128) void k_ensemble_reduce(const EnsembleReduce r)
+{
+    #pragma clang fp contract(off)
+    const int e = threadIdx.x, np = r.n_pcof, ld = np + 5, K = r.members;
+    if ((e < np && r.gradient) || e == np || e == np + 1) {
+        const double d = (double)(r.n_ess * r.n_ess);
+        double acc = r.first ? 0.0 : r.acc[e];
+        int k = 0;
+        for (; k + 4 <= K; k += 4) {
+            const double x0 = ensemble_entry(r.rows + (size_t)k * ld, e, np, r.infidelity, d), w0 = r.w[k];
+            const double x1 = ensemble_entry(r.rows + (size_t)(k + 1) * ld, e, np, r.infidelity, d), w1 = r.w[k + 1];
+            const double x2 = ensemble_entry(r.rows + (size_t)(k + 2) * ld, e, np, r.infidelity, d), w2 = r.w[k + 2];
+            const double x3 = ensemble_entry(r.rows + (size_t)(k + 3) * ld, e, np, r.infidelity, d), w3 = r.w[k + 3];
+            acc = acc + w0 * x0;
+            acc = acc + w1 * x1;
+            acc = acc + w2 * x2;
+            acc = acc + w3 * x3;
+        }
+        for (; k < K; k++) acc = acc + r.w[k] * ensemble_entry(r.rows + (size_t)k * ld, e, np, r.infidelity, d);
+        r.acc[e] = acc;
+    }
+    for (int t = threadIdx.x; t < 5 * K; t += blockDim.x) r.tails[t] = r.rows[(size_t)(t / 5) * ld + np + t % 5];
+}
+
 // ---------------------------------------------------------------------------
 // Derivative columns of lambda_history (optional output, qgd_set_lambda_derivatives).  The reference's eval_adjoint!
 // stores, beside lambda_n, the m "adjoint derivatives" it built the explicit side of step n from
@@ -678,6 +722,15 @@ int qgdk_contract_rows_batch(const qgdk_ctx *c, const qgdk_tiny_batch *b, int me
     ResultMirror none{};
     hipLaunchKernelGGL(k_contract_sum<true>, dim3((n_pcof + 15) / 16, members), dim3(1024), 0, c->stream, b->cpart, (double *)nullptr, n_pcof, rows,
                        0, (const int *)nullptr, (double *)nullptr, none, bt);
+    return (int)hipGetLastError();
+}
+
+// the weighted sums of an ensemble chunk behind it (k_ensemble_reduce), under the context's cost type
+int qgdk_ensemble_reduce(const qgdk_ctx *c, const double *rows, const double *weights, double *acc, double *tails, int members, int n_pcof, int first, int gradient)
+{
+    if (members < 1 || n_pcof < 1 || n_pcof + 2 > 128) return (int)hipErrorInvalidValue;
+    const EnsembleReduce r{rows, weights, acc, tails, members, n_pcof, first, gradient, c->cost_type == 0, c->n_ess};
+    hipLaunchKernelGGL(k_ensemble_reduce, dim3(1), dim3(128), 0, c->stream, r);
     return (int)hipGetLastError();
 }
 

@@ -30,6 +30,10 @@
 // templates on whether there is one (front: on where the coefficients come from), member b = blockIdx.y (scan: blockIdx.x) reads
 // and writes its own share of every per-evaluation array, TinyArgs::ms_* apart.  The arithmetic is one text: a member's bits
 // are the single evaluation's.
+//
+// An ENSEMBLE (qgd_eval_ensemble) is a batch whose members share the coefficients and differ in the
+// operator planes: the two kernels that stage the planes into LDS (front, grad) read member b's from ops + b * ms_ops, a
+// compile-time choice (PSRC::ens / ENS) that leaves the single call and the pcof batch reading c->ops with no stride.
 #include "qgd_kernels_common.h"
 #include <string.h>
 #include <algorithm>
@@ -254,17 +258,23 @@ __device__ __forceinline__ void matvecH(const double *__restrict__ Mx, const cx 
     }
 }
 
-// where k_tiny_front takes its coefficients from: the kernel arguments (one evaluation: no upload), or row b of a
-// device array [members][n_pcof] (a batch, qgd_eval_batch: member b = blockIdx.y)
+// where k_tiny_front takes its coefficients from: the kernel arguments (one evaluation: no upload), row b of a
+// device array [members][n_pcof] (a batch, qgd_eval_batch: member b = blockIdx.y), or the kernel arguments for every member
+// (an ensemble, qgd_eval_ensemble: one row, no upload; ens: the members' operator planes lie TinyArgs::ms_ops apart)
 template <int NMAX> struct TinyPcof {
     double v[NMAX];
-    static constexpr bool batch = false;
+    static constexpr bool batch = false, ens = false;
     __device__ __forceinline__ double at(int, int, int e) const { return v[e]; }
 };
 struct TinyPcofRows {
     const double *rows;
-    static constexpr bool batch = true;
+    static constexpr bool batch = true, ens = false;
     __device__ __forceinline__ double at(int b, int n_pcof, int e) const { return rows[(size_t)b * n_pcof + e]; }
+};
+template <int NMAX> struct TinyPcofShared {
+    double v[NMAX];
+    static constexpr bool batch = true, ens = true;
+    __device__ __forceinline__ double at(int, int, int e) const { return v[e]; }
 };
 
 struct TinyArgs {
@@ -289,6 +299,7 @@ struct TinyArgs {
     // a batch: member b's arrays lie b strides behind the pointers above (doubles; ms_status in ints)
     long long ms_tab, ms_mat, ms_cpart;         // tab; each of Rg, Linv, psi, lam; cpart
     int ms_scal, ms_status;
+    long long ms_ops;                           // an ensemble: member b's operator planes lie b strides behind ops
 };
 // member b's share of a per-member array (BATCH = false: the array itself, the stride is not read)
 template <bool BATCH, typename T>
@@ -300,7 +311,7 @@ __device__ __forceinline__ T *tiny_member(T *p, const int b, const long long str
 template <int M, int NO, int NMAX, class PSRC>
 __global__ __launch_bounds__(64) void k_tiny_front(const TinyArgs a, const PSRC pcof)
 {
-    constexpr bool BATCH = PSRC::batch;
+    constexpr bool BATCH = PSRC::batch, ENS = PSRC::ens;
     const int b = BATCH ? blockIdx.y : 0;               // (member arrays through tiny_member where they are used: pointers formed up
                                                         //  here stay live across the kernel and cost the single call four SGPRs)
     __shared__ double PC[NMAX], OPS[(2 + 2 * NO) * 16], TABS[(M + 1) * NO * 2], CW[2 * (M + 1)], Y[32];
@@ -314,7 +325,7 @@ __global__ __launch_bounds__(64) void k_tiny_front(const TinyArgs a, const PSRC 
     for (int e = tid; e < a.n_pcof; e += 64) PC[e] = pcof.at(b, a.n_pcof, e);
     for (int e = tid; e < (2 + 2 * n_ops) * 16; e += 64) {
         const int pl = e >> 4, r = (e >> 2) & 3, cc = e & 3;
-        OPS[e] = (r < N && cc < N) ? a.ops[(size_t)pl * a.Np * a.Np + r + (size_t)a.Np * cc] : 0.0;
+        OPS[e] = (r < N && cc < N) ? tiny_member<ENS>(a.ops, b, a.ms_ops)[(size_t)pl * a.Np * a.Np + r + (size_t)a.Np * cc] : 0.0;
     }
     if (tid < 2 * (M + 1)) CW[tid] = a.cwv[tid];
     if (tid >= 32 && tid < 36) { const int k = tid - 32; NC[k] = a.nc[k]; POFF[k] = a.po[k]; GOFF[k] = a.go[k]; }
@@ -687,7 +698,7 @@ __global__ __launch_bounds__(512) void k_tiny_scan(const TinyArgs a)
 // ---------------------------------------------------------------------------
 // grad: one workgroup (64 threads) per time point n; threads 0..3 = state columns
 // ---------------------------------------------------------------------------
-template <int M, int NO, bool BATCH>
+template <int M, int NO, bool BATCH, bool ENS = false>
 __global__ __launch_bounds__(64) void k_tiny_grad(const TinyArgs a)
 {
     const int b = BATCH ? blockIdx.y : 0;
@@ -704,7 +715,7 @@ __global__ __launch_bounds__(64) void k_tiny_grad(const TinyArgs a)
     double *TAB = TABS - n * TE, *SIG = SIGS - (size_t)n * n_ops * M * 2;
     for (int e = tid; e < (2 + 2 * n_ops) * 16; e += 64) {
         const int pl = e >> 4, r = (e >> 2) & 3, cc = e & 3;
-        OPS[e] = (r < N && cc < N) ? a.ops[(size_t)pl * a.Np * a.Np + r + (size_t)a.Np * cc] : 0.0;
+        OPS[e] = (r < N && cc < N) ? tiny_member<ENS>(a.ops, b, a.ms_ops)[(size_t)pl * a.Np * a.Np + r + (size_t)a.Np * cc] : 0.0;
     }
     if (tid < TE) TABS[tid] = tab_g[(size_t)n * TE + tid];
     if (tid < 2 * (M + 1)) CW[tid] = a.cwv[tid];
@@ -863,7 +874,7 @@ static int launch_tiny(const qgdk_ctx *c, TinyArgs &a, const PSRC &pc, size_t sh
     hipLaunchKernelGGL((k_tiny_front<M, NO, QGD_TINY_PCOF_MAX, PSRC>), dim3(c->nt, members), dim3(64), 0, c->stream, a, pc);
     SET_LDS_ONCE(k_tiny_scan<BATCH>, shm);
     hipLaunchKernelGGL(k_tiny_scan<BATCH>, dim3(members), dim3(threads), shm, c->stream, a);
-    if (a.gradient) hipLaunchKernelGGL((k_tiny_grad<M, NO, BATCH>), dim3(c->nt, members), dim3(64), 0, c->stream, a);
+    if (a.gradient) hipLaunchKernelGGL((k_tiny_grad<M, NO, BATCH, PSRC::ens>), dim3(c->nt, members), dim3(64), 0, c->stream, a);
     return (int)hipGetLastError();
 }
 template <class PSRC>
@@ -893,7 +904,7 @@ static void tiny_args(const qgdk_ctx *c, TinyArgs &a, int n_pcof, int gradient)
     a.gradient = gradient;
     a.dt = c->dt; a.tf = c->tf;
     a.mirror = nullptr; a.mirror_seq = 0;
-    a.ms_tab = a.ms_mat = a.ms_cpart = 0; a.ms_scal = a.ms_status = 0;
+    a.ms_tab = a.ms_mat = a.ms_cpart = 0; a.ms_scal = a.ms_status = 0; a.ms_ops = 0;
 }
 
 extern "C" {
@@ -931,10 +942,24 @@ int qgdk_tiny_eval(const qgdk_ctx *c, const double *pcof_host, int n_pcof, int g
     return launch_tiny_any(c, a, pc, doubles * sizeof(double), threads, 1);
 }
 
+// doubles of one ensemble member's operator planes: the layout of c->ops
+size_t qgdk_tiny_ensemble_planes(const qgdk_ctx *c) { return (2 + 2 * (size_t)c->n_ops) * c->Np * c->Np; }
+
 // doubles one member of a batch keeps on the device: tab | Rg, Linv, psi, lam | cpart | scal(4), status (QGD_TINY_BATCH_SMALL)
 void qgdk_tiny_batch_layout(const qgdk_ctx *c, int n_pcof, size_t *tab, size_t *mat, size_t *cpart)
 {
     *tab = (size_t)c->nt * (c->m + 1) * c->n_ops * 2; *mat = (size_t)c->nt * 32; *cpart = (size_t)c->nt * n_pcof;
+}
+
+// the per-member arrays of a batch and their strides
+static void tiny_batch_args(const qgdk_ctx *c, TinyArgs &a, const qgdk_tiny_batch *b, int n_pcof)
+{
+    size_t st, sm, sc;
+    qgdk_tiny_batch_layout(c, n_pcof, &st, &sm, &sc);
+    a.tab = b->tab; a.Rg = b->Rg; a.Linv = b->Linv; a.psi = b->psi; a.lam = b->lam; a.cpart = b->cpart;
+    a.scal = b->small; a.status = reinterpret_cast<int *>(b->small + 4);
+    a.ms_tab = (long long)st; a.ms_mat = (long long)sm; a.ms_cpart = (long long)sc;
+    a.ms_scal = QGD_TINY_BATCH_SMALL; a.ms_status = 2 * QGD_TINY_BATCH_SMALL;
 }
 
 // `members` evaluations with the coefficients b->pcofs[members][n_pcof] on the device, every per-member array of b one member
@@ -946,13 +971,25 @@ int qgdk_tiny_eval_batch(const qgdk_ctx *c, const qgdk_tiny_batch *b, int member
     size_t doubles; int threads;
     tiny_layout(c, a, doubles, threads);
     tiny_args(c, a, n_pcof, gradient);
-    size_t st, sm, sc;
-    qgdk_tiny_batch_layout(c, n_pcof, &st, &sm, &sc);
-    a.tab = b->tab; a.Rg = b->Rg; a.Linv = b->Linv; a.psi = b->psi; a.lam = b->lam; a.cpart = b->cpart;
-    a.scal = b->small; a.status = reinterpret_cast<int *>(b->small + 4);
-    a.ms_tab = (long long)st; a.ms_mat = (long long)sm; a.ms_cpart = (long long)sc;
-    a.ms_scal = QGD_TINY_BATCH_SMALL; a.ms_status = 2 * QGD_TINY_BATCH_SMALL;
+    tiny_batch_args(c, a, b, n_pcof);
     TinyPcofRows pc{b->pcofs};
+    return launch_tiny_any(c, a, pc, doubles * sizeof(double), threads, members);
+}
+
+// `members` evaluations of ONE coefficient vector (kernel arguments, as in qgdk_tiny_eval) over the operator planes
+// ops[members][(2 + 2 n_ops) Np Np] in the layout of c->ops; the per-member arrays are the batch's (b->pcofs is not read)
+int qgdk_tiny_eval_ensemble(const qgdk_ctx *c, const qgdk_tiny_batch *b, const double *ops, const double *pcof_host, int members, int n_pcof, int gradient)
+{
+    if (!qgdk_tiny_supported(c, n_pcof) || members < 1 || members > 65535) return (int)hipErrorInvalidValue;
+    TinyArgs a;
+    size_t doubles; int threads;
+    tiny_layout(c, a, doubles, threads);
+    tiny_args(c, a, n_pcof, gradient);
+    tiny_batch_args(c, a, b, n_pcof);
+    a.ops = ops; a.ms_ops = (long long)qgdk_tiny_ensemble_planes(c);
+    TinyPcofShared<QGD_TINY_PCOF_MAX> pc;
+    memset(&pc, 0, sizeof pc);
+    memcpy(pc.v, pcof_host, sizeof(double) * n_pcof);
     return launch_tiny_any(c, a, pc, doubles * sizeof(double), threads, members);
 }
 

@@ -4,14 +4,18 @@ frequencies, uncertain couplings, mis-calibrated drive amplitudes).  DESIGN.md s
 
   Ensemble(system_sym, system_asym, op_scale=None, weights=None)     the members; from_problems, member_problem
   ensemble_reduce(member_grads, member_out3, weights, cost_type, n_ess)   THE statement of the weighted sums
-  eval_ensemble / discrete_adjoint_ensemble(prob, controls, pcof, target, ensemble; order, cost_type)
+  eval_ensemble / discrete_adjoint_ensemble(prob, controls, pcof, target, ensemble; order, cost_type, route)
 
-Every member is evaluated on a handle of its own (``member_problem``), whatever its size and its controls, and the rows are
-reduced on the host by ensemble_reduce: a fixed statement, k ascending, every product and sum rounded on its own, so that
-a later device-side reduction has a definition to be bitwise equal to.
+Two routes, the same bits.  ``route="loop"``: every member is evaluated on a handle of its own (``member_problem``), whatever
+its size and its controls, and the rows are reduced on the host by ensemble_reduce: a fixed statement, k ascending, every
+product and sum rounded on its own.  ``route="device"``: the members run side by side on the handle of the problem itself
+(``DeviceProblem.set_ensemble`` / ``eval_ensemble``, qgd_eval_ensemble: small problems with controls linear in pcof), and the
+sums are formed on the device, bitwise equal to that statement; an objective then downloads one gradient per evaluation
+instead of K.  ``route="auto"`` (the default): the device where the library takes the problem, else the loop.
 """
 from __future__ import annotations
 
+import inspect
 import weakref
 
 import numpy as np
@@ -119,10 +123,42 @@ class Ensemble:
         return ent[2]
 
     def release_members(self, prob):
-        """Forget the members made for ``prob`` and close their handles."""
+        """Forget the members made for ``prob`` and close their handles; the cached handles of ``prob`` itself forget this
+        ensemble (the device route uploaded it there)."""
         ent = self._members.pop(id(prob), None)
         for mp in (ent[2] if ent else ()):
             _ev.release(mp)
+        for key, held in list(_ev._cache.items()):
+            if key[0] == id(prob) and held[0]() is prob:
+                set_on = getattr(held[1], "_ensemble", None)
+                if set_on is not None and set_on[0]() is self:
+                    held[1].set_ensemble(None)
+
+    def operator_arrays(self, sym_operators, asym_operators):
+        """What qgd_set_ensemble takes for these members of a problem with these control operators, no device involved:
+        ``(system_sym [K, N, N], system_asym [K, N, N], sym_ops [K, n_ops, N, N], asym_ops [K, n_ops, N, N], weights [K])``,
+        C-contiguous float64 with every matrix stored TRANSPOSED -- the column-major bytes of the matrix itself, as the
+        DeviceProblem constructor hands the operators of one problem over (the same ``_f`` conversion).  The control operators are
+        ``op_scale[k, o] * operator_o``, one multiply per entry (the arithmetic of member_problem); without ``op_scale`` they are
+        taken as they are.  The weights are ``effective_weights()``."""
+        K, N, n_ops = self.K, self.N, len(sym_operators)
+        if self.op_scale is not None and self.op_scale.shape[1] != n_ops:
+            raise ValueError(f"ensemble: op_scale has {self.op_scale.shape[1]} columns for {n_ops} control operators")
+        ss = np.ascontiguousarray(np.stack([_ev._f(self.system_sym[k]).T for k in range(K)]))
+        sa = np.ascontiguousarray(np.stack([_ev._f(self.system_asym[k]).T for k in range(K)]))
+        so, ao = np.zeros((K, max(n_ops, 1), N, N)), np.zeros((K, max(n_ops, 1), N, N))
+        for k in range(K):
+            for o in range(n_ops):
+                sym, asym = sym_operators[o], asym_operators[o]
+                if self.op_scale is not None:
+                    sym, asym = self.op_scale[k, o] * sym, self.op_scale[k, o] * asym
+                so[k, o], ao[k, o] = _ev._f(sym).T, _ev._f(asym).T
+        return ss, sa, so, ao, np.ascontiguousarray(self.effective_weights(), dtype=np.float64)
+
+    def device_arrays(self, prob):
+        """``operator_arrays`` for the control operators of ``prob``."""
+        self.check_problem(prob)
+        return self.operator_arrays(prob.sym_operators, prob.asym_operators)
 
     def member_problem(self, prob, k):
         """A SchrodingerProb copy of ``prob`` carrying member ``k``'s operators: its system Hamiltonian, and the control
@@ -179,17 +215,27 @@ def ensemble_reduce(member_grads, member_out3, weights, cost_type, n_ess):
 
 class EnsembleResult(tuple):
     """What the functional forms return: ``(grad or None, cost, guard)`` as a tuple, plus the members' rows ``member_grads``
-    ``[K, n_pcof]`` (or None) and ``member_out3`` ``[K, 3]``."""
+    ``[K, n_pcof]`` (or None) and ``member_out3`` ``[K, 3]`` (both None from an evaluation that asked for no rows), and the
+    ``route`` that produced them (``"loop"`` or ``"device"``)."""
 
-    def __new__(cls, grad, cost, guard, member_grads, member_out3):
+    def __new__(cls, grad, cost, guard, member_grads, member_out3, *, route="loop"):
         self = super().__new__(cls, (grad, cost, guard))
         self.grad, self.cost, self.guard = grad, cost, guard
-        self.member_grads, self.member_out3 = member_grads, member_out3
+        self.member_grads, self.member_out3, self.route = member_grads, member_out3, route
         return self
 
 
-def _evaluate(prob, controls, pcof, target, ensemble, order, cost_type, gradient):
+ROUTES = ("auto", "device", "loop")
+
+
+def _check_route(route):
+    if route not in ROUTES:
+        raise ValueError(f"route must be one of {ROUTES}; got {route!r}")
+
+
+def _evaluate(prob, controls, pcof, target, ensemble, order, cost_type, gradient, route="auto"):
     # every refusal that needs no device comes before a handle is asked for
+    _check_route(route)
     if not isinstance(ensemble, Ensemble):
         raise ValueError(f"ensemble must be an Ensemble; got {type(ensemble).__name__}")
     ensemble.check_problem(prob)
@@ -207,17 +253,52 @@ def _evaluate(prob, controls, pcof, target, ensemble, order, cost_type, gradient
         raise ValueError(f"pcof must have shape ({n_pcof},); got {pc.shape}")
     if gradient and target is None:
         raise ValueError("target: a gradient needs one")
-    return _loop_members(prob, controls, pc, target, ensemble, order, cost_type, gradient)
+    return _loop_members(prob, controls, pc, target, ensemble, order, cost_type, gradient, route=route, rows=True)
 
 
 _COST_NAMES = {0: "Infidelity", 1: "Tracking", 2: "Norm", 3: "StateTransfer"}
 
 
-def _loop_members(prob, controls, pc, target, ensemble, order, cost_type, gradient):
-    """One handle per member, then the statement on the host.  The members' problems are ``ensemble.member_problems(prob)``,
-    kept for the lifetime of ``prob``, so their handles stay in ``device_problem``'s cache from call to call (a loop of
-    evaluations pays for K handles once); ``release_members`` closes them.  A member's handle leaves with the cost type it
-    came with."""
+def _device_members(dp, controls, pc, target, ensemble, cost_type, gradient, rows):
+    """The members side by side on ``dp``, the handle of the problem itself, with its controls, target and cost type set; the
+    handle leaves with the cost type it came with."""
+    dp.set_controls(controls)
+    if target is not None:
+        dp.set_target(target)
+    before = _COST_NAMES[getattr(dp, "_cost_type", 0)]
+    dp.set_cost_type(cost_type)
+    try:
+        dp.set_ensemble(ensemble)
+        grad, cost, guard, mg, mo, _ = dp.eval_ensemble(pc, gradient=gradient, rows=rows)
+    finally:
+        dp.set_cost_type(before)
+    return EnsembleResult(grad, cost, guard, mg, mo, route="device")
+
+
+def _loop_members(prob, controls, pc, target, ensemble, order, cost_type, gradient, route="auto", rows=True):
+    """The members' evaluation, on the route asked for.
+
+    ``"device"``: side by side on the handle of ``prob`` itself (``_device_members``); ``rows=False`` leaves the members' rows on
+    the device.  ``"loop"``: one handle per member, then the statement on the host.  The members' problems are
+    ``ensemble.member_problems(prob)``, kept for the lifetime of ``prob``, so their handles stay in ``device_problem``'s cache
+    from call to call (a loop of evaluations pays for K handles once); ``release_members`` closes them.  A member's handle
+    leaves with the cost type it came with.  The loop always has the rows.  ``"auto"``: the device unless the nominal handle
+    forms its control tables on the host (controls that are not linear in pcof) or the library answers QGD_ERR_UNSUPPORTED
+    (anything but a small problem on the small-problem path); then the loop."""
+    _check_route(route)
+    if route == "device" or (route == "auto" and prob.N_tot_levels <= 4):      # (N > 4 is never the device's: no nominal handle is made for it)
+        E = _ev._lib
+        dp = _ev.device_problem(prob, order)
+        dp.set_controls(controls)
+        if getattr(dp, "_general", None):
+            if route == "device":
+                raise E.QGDError(E.QGD_ERR_UNSUPPORTED, "the device route of an ensemble needs controls linear in pcof")
+        else:
+            try:
+                return _device_members(dp, controls, pc, target, ensemble, cost_type, gradient, rows)
+            except E.QGDError as e:
+                if route == "device" or e.code != E.QGD_ERR_UNSUPPORTED:
+                    raise
     K = ensemble.K
     mg = np.zeros((K, len(pc))) if gradient else None
     mo = np.zeros((K, 3))
@@ -236,35 +317,44 @@ def _loop_members(prob, controls, pc, target, ensemble, order, cost_type, gradie
         finally:
             dk.set_cost_type(before)
     grad, cost, guard = ensemble_reduce(mg, mo, ensemble.weights, _ev.COST_TYPES[str(cost_type)], prob.N_ess_levels)
-    return EnsembleResult(grad, cost, guard, mg, mo)
+    return EnsembleResult(grad, cost, guard, mg, mo, route="loop")
 
 
 class EnsembleObjective:
-    """The robust objective of an optimiser: ``obj(pcof) -> (grad, cost, guard)``; ``close()`` closes the members' handles."""
+    """The robust objective of an optimiser: ``obj(pcof) -> (grad, cost, guard)``; ``close()`` closes the members' handles.  It
+    asks for no member rows: on the device route one gradient comes back per evaluation, not K."""
 
-    def __init__(self, prob, controls, target, ensemble, order, cost_type):
+    def __init__(self, prob, controls, target, ensemble, order, cost_type, route="auto"):
+        _check_route(route)
         if not isinstance(ensemble, Ensemble):
             raise ValueError(f"ensemble must be an Ensemble; got {type(ensemble).__name__}")
         ensemble.check_problem(prob)
         self.prob, self.controls, self.target, self.ensemble = prob, controls, target, ensemble
-        self.order, self.cost_type = order, cost_type
+        self.order, self.cost_type, self.route = order, cost_type, route
+        self._members, self._keywords = None, {}
 
     def __call__(self, pcof):
         pc = np.ascontiguousarray(pcof, dtype=np.float64)
-        res = _loop_members(self.prob, self.controls, pc, self.target, self.ensemble, self.order, self.cost_type, True)
+        members = _loop_members      # (the module global at the time of the call: a member evaluation put in its place counts)
+        if members is not self._members:
+            # one written against the eight positional arguments this function had before it took keywords is called as before
+            par = inspect.signature(members).parameters
+            takes = any(p.kind is inspect.Parameter.VAR_KEYWORD for p in par.values()) or {"route", "rows"} <= set(par)
+            self._members, self._keywords = members, (dict(route=self.route, rows=False) if takes else {})
+        res = members(self.prob, self.controls, pc, self.target, self.ensemble, self.order, self.cost_type, True, **self._keywords)
         return res.grad, res.cost, res.guard
 
     def close(self):
         self.ensemble.release_members(self.prob)
 
 
-def eval_ensemble(prob, controls, pcof, target, ensemble, order=2, cost_type="Infidelity", gradient=True):
+def eval_ensemble(prob, controls, pcof, target, ensemble, order=2, cost_type="Infidelity", gradient=True, route="auto"):
     """One ``pcof`` over the members of ``ensemble``: ``(grad or None, cost, guard)`` with ``cost = sum_k w_k cost_k``,
     ``guard = sum_k w_k guard_k`` and ``grad`` the gradient of their sum (ensemble_reduce is the statement).  The result also
-    carries ``member_grads`` and ``member_out3``."""
-    return _evaluate(prob, controls, pcof, target, ensemble, order, cost_type, gradient)
+    carries ``member_grads``, ``member_out3`` and the ``route`` it took (``route=``: "auto", "device" or "loop"; the same bits)."""
+    return _evaluate(prob, controls, pcof, target, ensemble, order, cost_type, gradient, route)
 
 
-def discrete_adjoint_ensemble(prob, controls, pcof, target, ensemble, order=2, cost_type="Infidelity"):
+def discrete_adjoint_ensemble(prob, controls, pcof, target, ensemble, order=2, cost_type="Infidelity", route="auto"):
     """eval_ensemble with the gradient: the robust counterpart of discrete_adjoint."""
-    return _evaluate(prob, controls, pcof, target, ensemble, order, cost_type, True)
+    return _evaluate(prob, controls, pcof, target, ensemble, order, cost_type, True, route)

@@ -163,6 +163,9 @@ class DeviceProblem:
         self._basis_key = None
         self._target_key = None
         self.n_pcof = 0
+        self.n_ess = prob.N_ess_levels
+        self._operators = (tuple(prob.sym_operators), tuple(prob.asym_operators))      # (set_ensemble scales them per member)
+        self._ensemble = None
 
     def close(self):
         self._finalizer()
@@ -584,6 +587,49 @@ class DeviceProblem:
         if rc != _lib.QGD_ERR_NUMERIC:
             _lib.check(self.h, rc)
         return grads, scalars, status
+
+    def set_ensemble(self, ensemble):
+        """qgd_set_ensemble: the members of ``ensemble`` (an ``Ensemble`` of this problem's size) become the handle's -- their
+        system Hamiltonians and the control operators ``op_scale[k, o] * operator_o`` (``Ensemble.operator_arrays``: the
+        arithmetic of ``member_problem``), and ``effective_weights()``.  ``None`` releases them.  Skipped when this very object
+        is already set; the library forgets an ensemble whenever the control basis or the time grid is set, so call this after
+        ``set_controls``."""
+        if ensemble is None:
+            self._ensemble = None
+            _lib.check(self.h, self.lib.qgd_set_ensemble(self.h, 0, None, None, None, None, None))
+            return
+        ent = self._ensemble
+        if ent is not None and ent[0]() is ensemble and ent[1] is self._basis_key and ent[1] is not None:
+            return
+        if ensemble.N != self.N:
+            raise ValueError(f"ensemble: the members have {ensemble.N} levels, the problem {self.N}")
+        ss, sa, so, ao, w = ensemble.operator_arrays(*self._operators)
+        self._ensemble = None
+        _lib.check(self.h, self.lib.qgd_set_ensemble(self.h, ensemble.K, _vp(ss), _vp(sa), _vp(so) if self.n_ops else None,
+                                                     _vp(ao) if self.n_ops else None, _vp(w)))
+        self._ensemble = (weakref.ref(ensemble), self._basis_key, ensemble.K)
+
+    def eval_ensemble(self, pcof, gradient=True, rows=True):
+        """qgd_eval_ensemble: ``pcof`` over the members set by ``set_ensemble``, side by side on the device, under the handle's
+        controls, target and cost type.  Returns ``(grad or None, cost, guard, member_grads, member_out3, status)``: the weighted
+        sums (``ensemble_reduce`` is their statement, bit for bit) and, with ``rows``, the members' rows ``[K, n_pcof]`` (None
+        without a gradient) and ``[K, 3]``, each what a handle made for that member returns; ``rows=False`` downloads neither
+        (both None).  ``status [K]`` int32 is 1 where a step matrix of that member was singular: that raises QGD_ERR_NUMERIC."""
+        if self._ensemble is None or self._ensemble[1] is not self._basis_key or self._basis_key is None:
+            raise _lib.QGDError(_lib.QGD_ERR_STATE, "set_ensemble must be called before eval_ensemble (and after set_controls)")
+        K = self._ensemble[2]
+        pc = np.ascontiguousarray(pcof, dtype=np.float64)
+        if pc.shape != (self.n_pcof,):
+            raise ValueError(f"pcof must have shape ({self.n_pcof},); got {pc.shape}")
+        grad = np.zeros(self.n_pcof) if gradient else None
+        out2 = np.zeros(2)
+        mg = np.zeros((K, self.n_pcof)) if rows and gradient else None
+        mo = np.zeros((K, 3)) if rows else None
+        status = np.zeros(K, dtype=np.int32)
+        rc = self.lib.qgd_eval_ensemble(self.h, _vp(pc), self.n_pcof, 1 if gradient else 0, None if grad is None else _vp(grad),
+                                        _vp(out2), None if mg is None else _vp(mg), None if mo is None else _vp(mo), _vp(status))
+        _lib.check(self.h, rc)
+        return grad, float(out2[0]), float(out2[1]), mg, mo, status
 
     def batch_path_taken(self):
         """Which route the last eval_batch call took: True the members side by side, False one after another."""
