@@ -566,5 +566,7 @@ int qgd_get_operator_path(qgd_handle h, int32_t *out3);
 #include "qgd_pushforward.h"
 /* one coefficient vector over the members of an ensemble side by side, reduced on the device */
 #include "qgd_ensemble.h"
+/* directional derivatives J v of the dense (between-grid) trajectory outputs */
+#include "qgd_dense_pushforward.h"
 
 #endif

@@ -432,6 +432,59 @@ function hip_eval_pushforward(prob::SchrodingerProb, controls, pcof::Vector{Floa
     return (states=states_dot, populations=pop_dot, expectations=expect_dot)
 end
 
+# qgd_eval_dense_pushforward (include/qgd_dense_pushforward.h) is called through its address for the same reason;
+# tests/test_dense_pushforward_host.py compares this call with its own header.
+qgd_eval_dense_pushforward_ptr() = Libdl.dlsym(Libdl.dlopen(libqgd), :qgd_eval_dense_pushforward)
+
+"Directional derivatives J v of the outputs of hip_eval_dense at `refine` points per step along the columns of `v` [n_pcof, n_vec]
+(or one vector) in pcof (qgd_eval_dense_pushforward): the forward-mode half of what hip_eval_dense_pullback transposes.  Returns
+the NamedTuple of hip_eval_pushforward with slots = 1 + nsteps*refine; slot 1 (the initial state) is exact zeros; independent of
+saveEveryNsteps; refine = 1 is hip_eval_pushforward of every grid point.  No target is needed.
+(Like the rest of this shim it was written against the headers without a Julia at hand: this wrapper has not been executed.)"
+function hip_eval_dense_pushforward(prob::SchrodingerProb, controls, pcof::Vector{Float64}, v::VecOrMat{Float64}; order::Int=2,
+                                    refine::Int=2, states::Bool=false, populations::Bool=false,
+                                    level_map::Union{Nothing,Matrix{Float64}}=nothing, observables=nothing,
+                                    history_precomputed::Bool=false)
+    refine >= 1 || throw(ArgumentError("refine must be >= 1"))
+    N, c, slots = prob.N_tot_levels, prob.N_initial_conditions, 1 + prob.nsteps * refine
+    V = v isa AbstractVector ? reshape(v, :, 1) : v
+    size(V, 1) == length(pcof) && size(V, 2) >= 1 || throw(DimensionMismatch("v must be [$(length(pcof))] or [$(length(pcof)), n_vec >= 1]"))
+    all(isfinite, V) || throw(ArgumentError("v must be finite"))
+    n_vec = size(V, 2)
+    level_map === nothing || size(level_map, 2) == N || throw(DimensionMismatch("level_map must be [n_groups, $N]"))
+    with_pop = populations || level_map !== nothing
+    states || with_pop || observables !== nothing || throw(ArgumentError("no output asked for"))
+    rows = level_map === nothing ? N : size(level_map, 1)
+    n_obs, has_im = 0, false
+    obs_re, obs_im = zeros(0, 0, 0), zeros(0, 0, 0)
+    if observables !== nothing
+        obs = observables isa AbstractMatrix ? [observables] : collect(observables)
+        n_obs = length(obs)
+        n_obs >= 1 || throw(ArgumentError("no observable"))
+        obs_re, obs_im = zeros(N, N, n_obs), zeros(N, N, n_obs)
+        for (j, o) in enumerate(obs)
+            size(o) == (N, N) || throw(DimensionMismatch("observable $j must be [$N, $N]"))
+            O = Matrix{ComplexF64}(o)
+            maximum(abs, O - O') <= 1e-12 * max(1.0, maximum(abs, O)) || throw(ArgumentError("observable $j is not Hermitian"))
+            obs_re[:, :, j] = real(O); obs_im[:, :, j] = imag(O)
+        end
+        has_im = any(!iszero, obs_im)
+    end
+    states_dot = states ? zeros(2N, slots, c, n_vec) : nothing
+    pop_dot = with_pop ? zeros(rows, slots, c, n_vec) : nothing
+    expect_dot = n_obs > 0 ? zeros(n_obs, slots, c, n_vec) : nothing
+    dp = device_problem(prob, order)
+    pc_ptr, pc_len = set_controls!(dp, prob, controls, pcof)
+    opt(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve pcof V states_dot pop_dot level_map expect_dot obs_re obs_im check(dp.handle, ccall(qgd_eval_dense_pushforward_ptr(), Cint,
+          (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64},
+           Ptr{Float64}, Ptr{Float64}, Int32),
+          dp.handle, pc_ptr, pc_len, history_precomputed ? 1 : 0, refine, pointer(V), n_vec, opt(states_dot), opt(pop_dot), opt(level_map),
+          level_map === nothing ? 0 : rows, opt(expect_dot), n_obs > 0 ? pointer(obs_re) : Ptr{Float64}(C_NULL),
+          has_im ? pointer(obs_im) : Ptr{Float64}(C_NULL), n_obs))
+    return (states=states_dot, populations=pop_dot, expectations=expect_dot)
+end
+
 "Gradient with respect to pcof of a cost written on the outputs of hip_eval_dense (qgd_eval_dense_pullback): sum of
 <bar, d output / d pcof> over the cotangents given, each in the shape of its dense output at `refine` points per step:
 states_bar [2N, 1+nsteps*refine, c]; populations_bar [N or n_groups, ..]; expectations_bar [n_obs, ..] with `observables` as

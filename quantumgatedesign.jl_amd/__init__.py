@@ -16,7 +16,7 @@ from .problems import (DispersiveProblem, construct_rabi_prob, construct_rand_pr
                        multi_qudit_hamiltonian_jayne, JaynesCummingsProblem, rotating_frame_qubit, dahlquist_problem)
 from .evolution import (DeviceProblem, device_problem, clear_cache, release, eval_forward, eval_forward_, eval_adjoint, eval_grad_forced, eval_grad_finite_difference, eval_hessian, eval_hessian_vec, discrete_adjoint,
                         get_populations, eval_populations, subsystem_population_map, eval_expectations, observable_planes, eval_pullback, pullback_cotangents,
-                        eval_dense, hermite_interpolate, hermite_dense_weights, dense_times, eval_dense_pullback, eval_pushforward, pushforward_directions,
+                        eval_dense, hermite_interpolate, hermite_dense_weights, dense_times, eval_dense_pullback, eval_pushforward, pushforward_directions, eval_dense_pushforward,
                         discrete_adjoint_batch, eval_objective_batch, batch_pcofs, finite_difference_points, finite_difference_quotient,
                         discrete_adjoint_, infidelity, infidelity_real, state_transfer_infidelity, COST_TYPES, guard_penalty_real, complex_to_real,
                         real_to_complex)

@@ -144,6 +144,9 @@ def lib():
     # include/qgd_pushforward.h (not in EXPORTS: that list is the entry points of qgd.h itself, which the tests enumerate)
     L.qgd_eval_pushforward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    # include/qgd_dense_pushforward.h (not in EXPORTS either)
+    L.qgd_eval_dense_pushforward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     # include/qgd_ensemble.h (not in EXPORTS either)
     L.qgd_set_ensemble.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.qgd_eval_ensemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

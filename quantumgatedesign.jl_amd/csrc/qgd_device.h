@@ -293,6 +293,11 @@ int qgdk_interp(const qgdk_ctx *c, const double *hist, const double *dpsi, doubl
    with G = -dJ/dd (qgdk_pullback_forcing) F is the forcing of qgdk_hvp_adjoint and qgdk_contract's minus gives the plus. */
 int qgdk_interp_transpose(const qgdk_ctx *c, const double *G, double *gbar, int refine, const double *w_dev);
 int qgdk_dense_pullback_sweep(const qgdk_ctx *c, const double *gbar, double *F, double *sigma);
+/* qgd_k_dense_pushforward.hip (qgd_eval_dense_pushforward): the tangent of the stage derivatives of c's history (hist, dpsi) along
+   the n_dir directions of a chunk -- sv [nt][Np][2 n_dir cp] the forced scan's tangent panels, gvt the direction table of
+   qgdk_hvp_gv_dirs -> dsv [nt][m][Np][2 n_dir cp], dw_1 .. dw_m in the layout of dpsi on a context with n_dir cp columns; every
+   panel is written, padding rows and columns as zeros.  N <= 64, m <= 8. */
+int qgdk_tangent_derivs(const qgdk_ctx *c, const double *sv, const double *gvt, double *dsv, int n_dir);
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 //   qgd_host_alloc.cpp    handles: creation, validation (SchrodingerProb.jl:73-154), the time grid and its windows, setters
 //   qgd_host_eval.cpp     one evaluation: forward / adjoint phases, result transport, the evaluation entry points
 //   qgd_host_sens.cpp     sensitivities of the state to the parameters: the forced gradient, the exact Hessian, Hessian-vector products, pullbacks (grid points and dense output); the refusals and the sweep they share with the pushforward
-//   qgd_host_pushforward.cpp  directional derivatives of the trajectory outputs (include/qgd_pushforward.h)
+//   qgd_host_pushforward.cpp  directional derivatives of the trajectory outputs, at the grid points (include/qgd_pushforward.h) and of the dense output (include/qgd_dense_pushforward.h)
 //   qgd_host_ensemble.cpp  one pcof over the members of an ensemble side by side, reduced on the device (include/qgd_ensemble.h)
 //   qgd_host_output.cpp   reference-layout output arrays of a resident or windowed grid: the copy stream, staging, the one transport; the rules of an OutputSelection
 //   qgd_host_windows.cpp  time grids in bounded memory: window entry, the windowed forward and adjoint passes
@@ -273,6 +273,15 @@ struct qgd_handle_s {
     double *redglob = nullptr;          // [n_pcof + 8] time shards: the reductions are out of place (send = the rank's own
                                         // [grad | scalars], receive = this), so a later history_precomputed call still finds
                                         // the rank's OWN guard sum and overlaps on the device, not the sums over the ranks
+    // qgd_eval_dense_pushforward, beside pf (scan buffers, direction table, uploads) and the dense panels and
+    // weight table of POOL_DENSE: the tangents of the stage derivatives of one chunk (dsv [nt][m] panels of the chunk's width), the
+    // interpolated tangent panels (dd [1 + (nt-1) refine]) and the staged outputs at their dense sizes, in a pool of their own
+    // that is one of the sensitivity pools (free_sensitivity_buffers releases it with pools[0 .. N_SENS_POOLS)); key (nt, n_pcof,
+    // basis directions, scan blocks, directions of a chunk, the lengths of the three staged outputs, refine, m, bits of dt).
+    // Pool and slots stand behind every other member: the members above keep their places, and the units that do not know the
+    // dense pushforward are compiled as before.
+    struct DensePushforwardBufs { double *dsv = nullptr, *dd = nullptr, *st = nullptr, *po = nullptr, *ex = nullptr; } dpf;
+    Pool dense_pushforward_pool;
 };
 
 namespace qgdh {

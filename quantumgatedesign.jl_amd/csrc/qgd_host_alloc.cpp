@@ -64,10 +64,11 @@ int pool_ensure(qgd_handle h, Pool &pool, const KeyedPlan &p, const char *fit, s
 }
 
 
-// the sensitivity pools (forced gradient, Hessian, Hessian-vector product, pullback, dense output, batch, dense pullback, pushforward) follow the grid and the control basis
+// the sensitivity pools (forced gradient, Hessian, Hessian-vector product, pullback, dense output, batch, dense pullback, pushforward, dense pushforward) follow the grid and the control basis
 void free_sensitivity_buffers(qgd_handle h)
 {
     for (int i = 0; i < N_SENS_POOLS; i++) pool_release(h->pools[i]);
+    pool_release(h->dense_pushforward_pool);
     hvp_void(h);
 }
 
@@ -583,6 +584,7 @@ void qgd_destroy(qgd_handle h)
     pool_release(h->pools[POOL_STAGE]);      // (first, as ever: the order of the frees shapes the addresses later allocations get)
     free_pool(h->static_bufs); free_pool(h->grid_bufs); free_pool(h->basis_bufs);
     for (Pool &pool : h->pools) pool_release(pool);
+    pool_release(h->dense_pushforward_pool);
     for (auto &p : h->phases) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     if (h->host_out) (void)hipHostFree(h->host_out);
     if (h->host_in) (void)hipHostFree(h->host_in);

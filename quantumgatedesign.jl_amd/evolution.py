@@ -500,6 +500,39 @@ class DeviceProblem:
                                                          opt(im), 0 if re is None else re.shape[2]))
         return {key: (a[..., 0] if single else a) for key, a in out.items()}
 
+    def eval_dense_pushforward(self, refine, pcof, v, states=False, populations=False, level_map=None, observables=None,
+                               history_precomputed=False):
+        """Pushforward of directions in pcof to the DENSE outputs: eval_pushforward for eval_dense_states,
+        eval_dense_populations (same ``level_map``) and eval_dense_expectations (same ``observables``) at ``refine`` points per
+        step.  Returns the dict of eval_pushforward, each part with ``1 + nsteps * refine`` slots and a trailing direction axis,
+        which a 1-D ``v`` drops.  Exact for the interpolant: the part that reaches the stage derivatives through the control
+        tables at their own grid point is included, so ``<ybar, J v> = <eval_dense_pullback(ybar), v>``.  Independent of
+        set_save_every; slot 0 is exact zeros; the grid slots of ``"states"`` are eval_pushforward's bits and ``refine = 1`` is
+        eval_pushforward of every grid point.  ``history_precomputed``: reuse the stored forward sweep when it belongs to this
+        pcof.  ``pcof=None``: tables and basis as they were set.  No target is needed."""
+        refine = check_refine(refine)
+        cols, single = pushforward_directions(v, self.n_pcof)
+        lm = None if level_map is None else level_map_array(level_map, self.N)
+        re, im = (None, None) if observables is None else observable_planes(observables, self.N)
+        if not (states or populations or lm is not None or re is not None):
+            raise ValueError("eval_dense_pushforward needs at least one of states, populations (or level_map), observables")
+        tail = (1 + self.nsteps * refine, self.c, cols.shape[1])
+        out = {}
+        if states:
+            out["states"] = np.zeros((2 * self.N,) + tail, order="F")
+        if populations or lm is not None:
+            out["populations"] = np.zeros((self.N if lm is None else lm.shape[0],) + tail, order="F")
+        if re is not None:
+            out["expectations"] = np.zeros((re.shape[2],) + tail, order="F")
+        pc, ptr, n = self._pcof_arg(pcof)
+        opt = lambda a: None if a is None else _vp(a)
+        _lib.check(self.h, self.lib.qgd_eval_dense_pushforward(self.h, ptr, n, 1 if history_precomputed else 0, refine, _vp(cols),
+                                                               cols.shape[1], opt(out.get("states")), opt(out.get("populations")),
+                                                               opt(lm), 0 if lm is None else lm.shape[0],
+                                                               opt(out.get("expectations")), opt(re), opt(im),
+                                                               0 if re is None else re.shape[2]))
+        return {key: (a[..., 0] if single else a) for key, a in out.items()}
+
     def eval_dense_pullback(self, refine, pcof=None, states_bar=None, populations_bar=None, level_map=None,
                             expectations_bar=None, observables=None, history_precomputed=False):
         """Pullback of the DENSE outputs to pcof: eval_pullback for a cost written on eval_dense_states,
@@ -1242,6 +1275,21 @@ def eval_pushforward(prob, controls, pcof, v, order=2, saveEveryNsteps=1, output
         out = dp.eval_pushforward(pcof, v, **asked)
     finally:
         dp.set_save_every(1)
+    return real_to_complex(out["states"]) if output == "states" else out[output]
+
+
+def eval_dense_pushforward(prob, controls, pcof, v, order=2, refine=2, output="states", level_map=None, observables=None):
+    """Directional derivative ``J v`` of an output of eval_dense at ``refine`` points per step along ``v`` in pcof: eval_pushforward
+    with ``slots = 1 + nsteps * refine`` (``output="states"``: complex ``[N, slots, N_initial_conditions]``; ``"populations"``,
+    ``"expectations"``: real), ``v`` ``(n_pcof,)`` or ``(n_pcof, n_vec)`` (DeviceProblem.eval_dense_pushforward, DESIGN.md section
+    4n).  Exact for the interpolant, unlike differences of eval_dense.  Not in the reference."""
+    refine = check_refine(refine)
+    # (refusals before a handle is made or anything is uploaded)
+    asked = pushforward_outputs(prob.N_tot_levels, output, level_map, observables)
+    pushforward_directions(v, len(np.asarray(pcof).reshape(-1)))
+    dp = device_problem(prob, order)
+    dp.set_controls(controls)
+    out = dp.eval_dense_pushforward(refine, pcof, v, **asked)
     return real_to_complex(out["states"]) if output == "states" else out[output]
 
 
